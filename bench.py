@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark (BASELINE.json): sampled clips/sec, 3 dancers x 150 frames, 1000 DDPM steps.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 One "step" = one full `GaussianDiffusion.p_sample_loop` (hoisted music encoder + 1000 guided denoising steps +
 the result all-gather) over a batch of 16 synthetic clips per GPU, bf16 MFMA operands.  Inputs (weights, music
@@ -14,10 +14,13 @@ each), waits, relays rank 0's JSON line and exits non-zero if any rank failed.  
 index, no collective inside the loop, one RCCL all-gather at the end; the timed region is bracketed by barrier +
 synchronize and the MAX over ranks is reported.
 
-Rank 0 prints ONE JSON line: whole-job throughput, `roofline` for the kernel with the largest share of GPU time
-(algorithmic FLOPs / its average duration INSIDE the running sampler, against the 2.5 PFLOP/s dense bf16 MFMA peak;
-the HBM figure is secondary), `parity_mode` (the f32 mode that carries the <= 1e-3 claim, timed here too) and, at
-N = 1, `cpu_baseline` (the CPU oracle -- a port of the reference's PyTorch path -- on the host cores).
+Rank 0 prints ONE JSON line: whole-job throughput (`value`, clips/s) and `ms_per_step`, the time of one timed step.  A plain
+run does nothing else: set up, warm up, time the K steps, write the outputs (`--dump-outputs DIR`: the gathered samples of the
+last timed step as DIR/samples.npy) and print the line.  `--full` adds the secondary measurements: `roofline` for the kernel
+with the largest share of GPU time (algorithmic FLOPs / its average duration INSIDE the running sampler, against the
+2.5 PFLOP/s dense bf16 MFMA peak; the HBM figure is secondary), `parity_mode` (the f32 mode that carries the <= 1e-3 claim,
+timed here too), the benchmarked arithmetic against the reference's outputs, at N = 1 `cpu_baseline` (the CPU oracle -- a
+port of the reference's PyTorch path -- on the host cores) and `other_configs`, and the training step.
 """
 import argparse
 import importlib.util
@@ -46,6 +49,13 @@ def parse(argv=None):
     p.add_argument("--frames", type=int, default=150)
     p.add_argument("--ddpm-steps", type=int, default=1000)
     p.add_argument("--dtype", default="bf16", choices=["bf16", "f32", "bf16x3"])
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements (per-kernel roofline passes, the f32 / bf16x3 modes, the comparison "
+                        "with the reference outputs, the CPU baseline, the other configurations, the training step); the "
+                        "--no-* options below switch single ones off again")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="rank 0 writes the gathered samples of the last timed step as DIR/samples.npy (float32, at most 64 MB: "
+                        "a fixed seeded choice of whole clips beyond that)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-parity-mode", action="store_true", help="skip the f32-mode timing")
     p.add_argument("--no-kernel-profile", action="store_true", help="skip the in-sampler per-kernel timing pass")
@@ -425,6 +435,25 @@ def cpu_baseline(dn, S, T, seconds):
 
 
 # ----------------------------------------------------------------------------------------------------------------
+# outputs of the timed path
+# ----------------------------------------------------------------------------------------------------------------
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(d, samples, max_bytes=DUMP_MAX_BYTES):
+    """`--dump-outputs DIR`: the gathered samples (clips, tokens, 151) of the last timed step as DIR/samples.npy, float32.
+    Larger than `max_bytes`: whole clips chosen by a fixed seed, in clip order (the same clips for the same arguments)."""
+    import numpy as np
+    x = samples.detach().float().cpu().numpy()
+    per_clip = x[0].nbytes if len(x) else 1
+    if x.nbytes > max_bytes:
+        keep = np.sort(np.random.default_rng(0).choice(len(x), max(1, max_bytes // per_clip), replace=False))
+        x = x[keep]
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "samples.npy"), np.ascontiguousarray(x, dtype=np.float32))
+
+
+# ----------------------------------------------------------------------------------------------------------------
 # rank body
 # ----------------------------------------------------------------------------------------------------------------
 def rank_facts(D, n_total, rank, world, dev):
@@ -497,7 +526,6 @@ def rank_main(a):
     cond = torch.stack([W.synth_cond(c, S) for c in range(lo, hi)]).to(dev)
     xT = torch.stack([W.synth_xT(c, Lq) for c in range(lo, hi)]).to(dev)
     ranks_seen, clip_ranges = rank_facts(D, n_total, rank, world, dev)
-    xT0, cond0 = W.synth_xT(0, Lq)[None].to(dev), W.synth_cond(0, S)[None].to(dev)       # clip 0 (the goldens' clip)
 
     def one_job():
         x = diff.p_sample_loop((hi - lo, Lq, 151), cond, noise=xT, seed=1234, clip_offset=lo)
@@ -519,6 +547,8 @@ def rank_main(a):
     assert out.shape == (n_total, Lq, 151) and bool(torch.isfinite(out).all())
     if a.dump_samples and rank == 0:
         torch.save(out.cpu(), a.dump_samples)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, out)
 
     if rank == 0:
         clips_per_s = n_total * a.steps / dt
@@ -554,7 +584,7 @@ def rank_main(a):
                                  "executed_tflops_per_gpu": round(clips_per_s / world * gf_exec * T / 1e3, 2),
                                  "executed_mfma_frac_per_gpu": round(clips_per_s / world * gf_exec * T / 1e3 / peak, 4)}
         roof, rows = None, {}
-        if not a.no_kernel_profile and T >= 200:
+        if a.full and not a.no_kernel_profile and T >= 200:
             # Launch durations and HBM-side bytes from rocprofv3 passes over a child run of this very command (the same files a
             # `rocprofv3 --kernel-trace --stats` of it gives: profiles/rNN_kernel_stats_*): `frac` is reproducible from them and the
             # family sum fits the wall time.  torch.profiler inside this process is the fallback (it inflates launches by 4-5 %).
@@ -586,9 +616,10 @@ def rank_main(a):
                                                              f"through sampler update; setup and warm-up excluded)"}
                 if prof.get("errors"):
                     roof["profiler_pass_errors"] = prof["errors"]
-        res["roofline"] = roof
-        res["kernels"] = rows
-        if world == 1 and not a.no_parity_mode and a.dtype == "bf16" and T >= 200:
+        if a.full:
+            res["roofline"] = roof
+            res["kernels"] = rows
+        if a.full and world == 1 and not a.no_parity_mode and a.dtype == "bf16" and T >= 200:
             # the two modes held to <= 1e-3 against the reference, timed on the same workload: "f32" (v_mfma_f32_32x32x2_f32, an
             # exact fp32 fma chain) and "bf16x3" (fp32 storage, every product as three bf16 MFMAs on (hi, lo) splits)
             pm = {}
@@ -609,12 +640,13 @@ def rank_main(a):
             pm["bf16x3"]["mfma_frac_bf16_peak_executed"] = \
                 round(3 * pm["bf16x3"]["value"] * gf * T / 1e3 / PEAK_BF16_TFLOPS, 4) if gf else None
             res["parity_mode"] = dict(pm["f32"], fast=pm["bf16x3"])
-        if world == 1 and (dn, S, T) == (3, 150, 1000):
+        if a.full and world == 1 and (dn, S, T) == (3, 150, 1000):
             # how far the BENCHMARKED arithmetic is from the reference: one guided evaluation of clip 0 at two timesteps against
             # the committed outputs of the real reference on the same name-keyed synthetic weights and inputs
             # (tests/golden/c2_forward.npz, made by tests/golden/make_golden.py); asserted in tests/test_parity_gpu.py
             try:
                 import numpy as np
+                xT0, cond0 = W.synth_xT(0, Lq)[None].to(dev), W.synth_cond(0, S)[None].to(dev)   # clip 0 (the goldens' clip)
                 gz = np.load(os.path.join(ROOT, "tests", "golden", "c2_forward.npz"))
                 errs = {}
                 for t in (999, 37):
@@ -626,9 +658,9 @@ def rank_main(a):
                     bound_in_tests=2.5e-2 if a.dtype == "bf16" else 5e-4)
             except Exception as e:
                 res["vs_reference_error"] = repr(e)[:300]
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(dn, S, T, a.cpu_seconds)
-        if world == 1 and not a.no_other_configs and (dn, S, T) == (3, 150, 1000):
+        if a.full and world == 1 and not a.no_other_configs and (dn, S, T) == (3, 150, 1000):
             # BASELINE.json's other single-GPU sampling configurations, one timed job each after a warm-up job (they are
             # parity-test cases, not the metric: reported so that a driver run sees what DESIGN.md section 5 quotes)
             try:
@@ -637,7 +669,7 @@ def rank_main(a):
                 res["other_configs_error"] = repr(e)[:300]
     # ---- secondary: the training step (BASELINE config 5: batch 32 per GPU, Adan, data-parallel over the job's ranks) ----------
     ts, ts_err = None, None
-    if not a.no_train_step:
+    if a.full and not a.no_train_step:
         try:
             ts = train_step_bench(a, D, dev, world, dn, S)
         except Exception as e:           # the headline line must not depend on the secondary measurement

@@ -51,3 +51,26 @@ def test_roofline_from_a_synthetic_trace():
 def test_child_mode_is_an_option_of_the_same_script():
     a = bench.parse(["--child-steps", "40", "--batch", "16"])
     assert a.child_steps == 40 and a.gpus == 1
+
+
+def test_plain_run_is_the_headline_only_and_full_is_opt_in():
+    a = bench.parse(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert a.steps == 5 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", "out", "--no-cpu-baseline"])
+    assert a.full and a.dump_outputs == "out" and a.no_cpu_baseline
+
+
+def test_dump_outputs_writes_float32_and_caps_the_size(tmp_path):
+    import numpy as np
+    import torch
+    x = torch.arange(10 * 4 * 3, dtype=torch.float32).reshape(10, 4, 3)
+    bench.dump_outputs(str(tmp_path / "all"), x)
+    got = np.load(tmp_path / "all" / "samples.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, x.numpy())
+    cap = 3 * x[0].numel() * 4                                   # room for three clips: a fixed choice of whole clips
+    bench.dump_outputs(str(tmp_path / "a"), x, max_bytes=cap)
+    bench.dump_outputs(str(tmp_path / "b"), x.double(), max_bytes=cap)
+    a, b = np.load(tmp_path / "a" / "samples.npy"), np.load(tmp_path / "b" / "samples.npy")
+    assert a.shape == (3, 4, 3) and a.nbytes <= cap and np.array_equal(a, b)
+    starts = a[:, 0, 0] / 12
+    assert list(starts) == sorted(starts) and all(np.array_equal(c, x[int(s)].numpy()) for c, s in zip(a, starts))

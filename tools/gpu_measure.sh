@@ -9,7 +9,7 @@ python -m pytest tests/test_parity_gpu.py -m gpu -s -q -k "c2 or bf16 or drift" 
 if [ -z "$SKIP_TRAIN" ]; then
 python -m pytest tests/test_train_step_gpu.py -m gpu -s -q 2>&1 | grep -E "\[f32\]|\[bf16|passed|failed" > gpurun_out/${R}_train_step_parity.log; tail -3 gpurun_out/${R}_train_step_parity.log
 fi
-python bench.py 2>gpurun_out/bench_default_err.log > gpurun_out/${R}_bench_full_1000steps.json; tail -c 2500 gpurun_out/${R}_bench_full_1000steps.json
+python bench.py --full 2>&1 | tail -c 2500
 python tools/chain_full_bench.py --forms 8 --reps 3 2>/dev/null | grep "waves:" > gpurun_out/${R}_chain_block_scaling.txt; cat gpurun_out/${R}_chain_block_scaling.txt
 if [ -z "$SKIP_TRAIN" ]; then for b in 4 32; do python tools/train_bench.py --batch $b --iters 8 --kernels 2>/dev/null | tail -1; done > gpurun_out/${R}_train_step.jsonl; cut -c1-400 gpurun_out/${R}_train_step.jsonl; fi
 ARGS="bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-kernel-profile --no-parity-mode --no-train-step --no-other-configs"
@@ -22,7 +22,7 @@ rm -rf gpurun_out/prof_trace
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_c4 -- python3 $ARGS --batch 4 --dancers 5 --frames 300 --ddpm-steps 60 > gpurun_out/prof_c4.log 2>&1
 f=$(find gpurun_out/prof_c4 -name "*kernel_stats.csv" | head -1); cp "$f" gpurun_out/${R}_kernel_stats_config4_5x300_b4_60steps.csv; head -8 "$f" | cut -c1-160
 rm -rf gpurun_out/prof_c4
-# (roofline: bench.py runs the kernel-trace / FETCH_SIZE / WRITE_SIZE child passes itself; the default run above carries them)
+# (roofline: bench.py --full runs the kernel-trace / FETCH_SIZE / WRITE_SIZE child passes itself; the --full run above carries them)
 SETS="SQ_LDS_BANK_CONFLICT,SQ_LDS_IDX_ACTIVE,SQ_INSTS_LDS SQ_VALU_MFMA_BUSY_CYCLES,SQ_INSTS_VALU,SQ_INSTS_MFMA,SQ_BUSY_CYCLES" bash tools/gpu_pmc2.sh > /dev/null 2>&1
 cp gpurun_out/pmc2_summary.txt gpurun_out/${R}_pmc_SQ_counters_20steps.txt; head -8 gpurun_out/${R}_pmc_SQ_counters_20steps.txt | cut -c1-250
 if [ -z "$SKIP_TRAIN" ]; then

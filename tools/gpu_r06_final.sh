@@ -4,7 +4,7 @@ mkdir -p gpurun_out
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:?}"
 ( time timeout 3000 python -m pytest tests -q -m gpu 2>&1 | tail -4 ) 2>&1 | tee gpurun_out/r06_gpu_suite_final.log
 timeout 900 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -6 | tee gpurun_out/r06_smoke.log
-python bench.py 2>gpurun_out/bench_default_err.log > gpurun_out/r06_bench_full_1000steps.json; tail -c 1200 gpurun_out/r06_bench_full_1000steps.json
+python bench.py --full 2>&1 | tail -c 1200
 timeout 900 python bench.py --steps 20 --warmup 2 --no-pmc --no-kernel-profile --no-parity-mode --no-cpu-baseline --no-train-step --no-other-configs 2>/dev/null | tail -1 | cut -c1-200 | tee gpurun_out/r06_bench_20jobs.txt
 ARGS="bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-kernel-profile --no-parity-mode --no-train-step --no-other-configs"
 rm -rf gpurun_out/prof_trace

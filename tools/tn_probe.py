@@ -1,5 +1,5 @@
 import os, sys
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from tcdiff_amd import _lib as L, kernels as K
 dev, bf = "cuda", torch.bfloat16
