@@ -296,6 +296,7 @@ class GaussianDiffusion(nn.Module):
                 K.window_couple_step(st["x"], B, couple[0], couple[1], st["counter"], st["params"])
 
         graphs = self.__dict__.setdefault("_graphs", {})
+        is_step_key = lambda k: isinstance(k, tuple) and len(k) > 2 and k[0] != "warm"    # (the warm-up marks are ("warm", key))
         gen = eng.generation
         q_noise = constrain.get("q_noise") if constrain is not None else None
         # Every per-step quantity lives in device memory (counter, step tables, seed), so one captured graph serves every step -- and
@@ -322,7 +323,12 @@ class GaussianDiffusion(nn.Module):
                 st["qeps"].copy_(q_noise(int(t), (B, Lq, nf)).reshape(B * Lq, nf))
             # (the constraint kernel is captured reading st["cparams"] or st["params"]: part of the key -- ADVICE r5)
             ckey = None if constrain is None else (constrain["kind"], q_noise is not None, mask_rows, constrain.get("params") is not None)
-            gkey = (mode, branches, step_noise is not None, traj is not None, clip_offset, B, gen, id(self.model), ckey, couple, u)
+            # (the kernel form the engine resolves from its switches at every forward -- small-job layers, parts 1 + 2 merged, the
+            # fragment front, the forked prologue -- is part of the key too: a switch changed after a capture must not replay the old form)
+            split = eng._split_job(branches * B)
+            form = (split, split and eng._merge12(Lq), split and eng.front and os.environ.get("TCDIFF_SPLIT_FRONT", "1") != "0",
+                    os.environ.get("TCDIFF_FORK_PROLOGUE", "0") == "1")
+            gkey = (mode, branches, step_noise is not None, traj is not None, clip_offset, B, gen, id(self.model), ckey, couple, u, form)
             if not use_graph:
                 step(branches)
             elif gkey in graphs:
@@ -332,9 +338,9 @@ class GaussianDiffusion(nn.Module):
                     step(branches)              # first visit: eager (loads code objects, sets kernel attributes)
                 graphs[("warm", gkey)] = True
             else:                               # second visit: capture once, replay from now on
-                for k in [k for k in graphs if isinstance(k, tuple) and len(k) == 11 and k[7] == id(self.model) and k[6] != gen]:
+                for k in [k for k in graphs if is_step_key(k) and k[7] == id(self.model) and k[6] != gen]:
                     del graphs[k]               # graphs of engines whose buffers have moved
-                live = [k for k in graphs if isinstance(k, tuple) and len(k) == 11]
+                live = [k for k in graphs if is_step_key(k)]
                 for k in live[:max(0, len(live) - 15)]:
                     del graphs[k]               # a bounded cache: at most 16 captured step graphs (oldest first) ...
                     graphs.pop(("warm", k), None)   # ... and their warm-up marks
@@ -444,7 +450,9 @@ class GaussianDiffusion(nn.Module):
 
         Extra keyword-only arguments: ``step_noise(t, shape)`` injects the per-step N(0,1) draw (parity tests);
         otherwise eps comes from an in-kernel Philox stream keyed by (seed, clip_offset + clip, t, element), so
-        the samples of a clip do not depend on the batch it is in or on how clips are sharded over GPUs."""
+        the NOISE of a clip does not depend on the batch it is in or on how clips are sharded over GPUs.  Its sample does in
+        bf16 only: the per-rank job size picks the kernel family of the decoder layers (small jobs: tcdiff_chain_split), another
+        fp32 summation order, so a clip sampled alone and inside a larger job differ by bf16 rounding (f32 / bf16x3: identical)."""
         device = self._device()
         start_point = self.n_timestep if start_point is None else start_point
         x = torch.randn(shape, device=device) if noise is None else noise.to(device)

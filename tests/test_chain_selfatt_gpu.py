@@ -5,7 +5,6 @@ head-major Q / K / V images + the attention kernel, which tests/test_chain_gpu.p
 reference)."""
 import os
 
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
@@ -17,6 +16,7 @@ from tcdiff_amd import _lib as L  # noqa: E402
 from tcdiff_amd import kernels as K  # noqa: E402
 from tcdiff_amd.engine import DenoiserEngine as E  # noqa: E402
 from tcdiff_amd.model import DanceDecoder  # noqa: E402
+from layer_ref import kf_index, unpack_kv, unpack_q, vf_index  # noqa: E402,F401  (the fragment maps: tests/layer_ref.py)
 
 DEV = "cuda"
 bf = torch.bfloat16
@@ -32,36 +32,6 @@ def folded(film, specs):
     for off, (g, b) in specs.items():
         out[:, off:off + 1024] = K.fold_film(film[:, off:off + 1024], g, b)
     return out
-
-
-# element maps of the fragment images (csrc/ops.hip kf_index / vf_index; tests/test_chain_layout_cpu.py checks them against
-# plain matrix products)
-def kf_index(key, d):
-    kt, k32, d32 = key >> 5, key & 31, d & 31
-    g, jj = (d32 & 15) >> 2, 4 * (d32 >> 4) + (d32 & 3)
-    return (((kt * 2 + (k32 >> 4)) * 2 + (d >> 5)) * 64 + g * 16 + (k32 & 15)) * 8 + jj
-
-
-def vf_index(key, d):
-    kt, k32 = key >> 5, key & 31
-    g, jj = (k32 & 15) >> 2, 4 * (k32 >> 4) + (k32 & 3)
-    return ((kt * 4 + (d >> 4)) * 64 + g * 16 + (d & 15)) * 8 + jj
-
-
-def unpack_kv(img, fn, nkeys):
-    """[n_seq, H, nkt * 2048] fragment image -> [n_seq, H, nkeys, 64]"""
-    key, d = np.meshgrid(np.arange(nkeys), np.arange(64), indexing="ij")
-    idx = torch.from_numpy(fn(key, d).astype(np.int64)).to(img.device)
-    return img[:, :, idx.reshape(-1)].reshape(img.shape[0], img.shape[1], nkeys, 64)
-
-
-def unpack_q(qf, nseq, Lq, rows):
-    """[blocks, 8 waves, 4 (rows / 16 of them used), 2, 64 lanes, 8] -> [n_seq, H, Lq, 64] (the valid rows of every block)"""
-    nbs = (Lq + rows - 1) // rows
-    q = qf[:, :, :rows // 16].reshape(nseq, nbs, 8, rows // 16, 2, 4, 16, 2, 4)            # seq, block, head, mt, s, g, c, jj >> 2, jj & 3
-    # row = rows b + 16 mt + c ; d = 32 s + 16 (jj >> 2) + 4 g + (jj & 3)
-    q = q.permute(0, 2, 1, 3, 6, 4, 7, 5, 8).reshape(nseq, 8, nbs * rows, 64)
-    return q[:, :, :Lq]
 
 
 class Layer:
