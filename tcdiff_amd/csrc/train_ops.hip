@@ -881,8 +881,12 @@ __global__ __launch_bounds__(64) void fk_bwd_kernel(const float* __restrict__ mo
     }
     fk_backward(aa, sk, d_j + i * 72, g_aa, g_root);
     float* o = d_out + i * C;
-    o[4] += g_root[0]; o[5] += g_root[1]; o[6] += g_root[2];
+    {
+#pragma clang fp contract(off)      // d_out += g is a plain float32 add of the finished gradient, never fused into its last product
+        o[4] += g_root[0]; o[5] += g_root[1]; o[6] += g_root[2];
+    }
     for (int j = 0; j < TC_FK_J; ++j) {
+#pragma clang fp contract(off)
         float g6[6];
         ax_from_6v_bwd(row + 7 + 6 * j, v3(g_aa[3 * j], g_aa[3 * j + 1], g_aa[3 * j + 2]), g6);
 #pragma unroll
