@@ -40,7 +40,11 @@ typedef struct ihipStream_t* hipStream_t;
 #define TC_DTYPE_BF16X3 2 /* tcdiff_gemm_tile (forward epilogues), tcdiff_gemm_rowln, tcdiff_attention only: operands stored as fp32
                              exactly as for TC_DTYPE_F32; every product a b is formed as a_hi b_hi + a_hi b_lo + a_lo b_hi with
                              a_hi = bf16(a), a_lo = bf16(a - a_hi) -- three bf16 MFMAs, fp32 accumulate: ~2^-16 per product, the
-                             reference's fp32 path (model/model.py:548-624 runs without autocast) to well inside 1e-3 */
+                             reference's fp32 path (model/model.py:548-624 runs without autocast) to well inside 1e-3.
+                             A 16-byte chunk of four elements is stored as [hi x4 | lo x4], so a T-typed row starts on a
+                             chunk: tcdiff_gemm_tile's TC_EPI_STORE_T needs ldc % 4 == 0 (a partial last chunk of N % 4
+                             elements is written element by element), tcdiff_convert_pad / tcdiff_step_prologue ld_dst /
+                             ld_xin % 4 == 0; TC_ERR_ARG otherwise */
 
 /* activations (fused into GEMM epilogues and elementwise helpers) */
 #define TC_ACT_NONE 0

@@ -100,6 +100,7 @@ struct MmaBF16x3 {
     static constexpr bool IS_BF16 = false;
     static constexpr bool IS_X3 = true;
     static DEVINL u32x4 chunk_from4(const f32x4_t& f) {
+#pragma clang fp contract(off)   // lo splits the fp32 value: a product feeding f must not fuse into the f - hi below
         const uint32_t h01 = pack_bf2(f[0], f[1]), h23 = pack_bf2(f[2], f[3]);      // round to nearest even
         const float g0 = __builtin_bit_cast(float, h01 << 16), g1 = __builtin_bit_cast(float, h01 & 0xFFFF0000u);
         const float g2 = __builtin_bit_cast(float, h23 << 16), g3 = __builtin_bit_cast(float, h23 & 0xFFFF0000u);
@@ -138,6 +139,7 @@ struct MmaBF16x3 {
 template <class P>
 DEVINL void store_T(typename P::elem_t* base, long i, float v) {
     if constexpr (std::is_same<P, MmaBF16x3>::value) {
+#pragma clang fp contract(off)   // as MmaBF16x3::chunk_from4: lo = bf16(v - hi) of the fp32 v
         const uint16_t hi = f2bf(v);
         uint16_t* c = reinterpret_cast<uint16_t*>(base) + (i >> 2) * 8 + (i & 3);
         c[0] = hi;

@@ -418,6 +418,16 @@ __global__ __launch_bounds__(256) void gemm_tile_kernel(const char* __restrict__
                 *reinterpret_cast<u32x4*>(d2) = pack_chunk<P>(y);
             } else if (n + EPC <= N && (qkv || ((long)e.ldc * ES) % 16 == 0)) {
                 *reinterpret_cast<u32x4*>(dst) = val;
+            } else if constexpr (P::IS_X3) {
+                // a partial chunk of the split format (the launcher keeps rows chunk-aligned): an element's hi and lo are the 2-byte
+                // halves t and 4 + t of the chunk, not a 4-byte slot -- copied element by element, nothing past N is touched
+                const uint16_t* sv = reinterpret_cast<const uint16_t*>(smem + row * RS + ch * 16);
+                uint16_t* d16 = reinterpret_cast<uint16_t*>(dst);
+                for (int t = 0; t < EPC; ++t)
+                    if (n + t < N) {
+                        d16[t] = sv[t];
+                        d16[4 + t] = sv[4 + t];
+                    }
             } else {
                 const T* sv = reinterpret_cast<const T*>(smem + row * RS + ch * 16);
                 for (int t = 0; t < EPC; ++t)
@@ -856,6 +866,9 @@ static int launch_tile(int dtype, const void* A, const void* A2, int split_n, co
     // TC_DTYPE_BF16X3: fp32 storage (every size and alignment rule of TC_DTYPE_F32), products as split-bf16 triples; the plain
     // forward epilogues only (the sampler's path: no split-K, no fused training epilogues)
     if (dtype == TC_DTYPE_BF16X3 && (epi->mode == TC_EPI_ATOMIC_F32 || epi->out2 || epi->act_src)) return TC_ERR_UNSUPPORTED;
+    // a split chunk holds four elements as [hi x4 | lo x4]: its 4-byte slots are not elements, so a STORE_T row has to start on a
+    // chunk (a partial last chunk is written element by element in the epilogue)
+    if (dtype == TC_DTYPE_BF16X3 && epi->mode == TC_EPI_STORE_T && epi->ldc % 4) return TC_ERR_ARG;
     const int es = dtype == TC_DTYPE_BF16 ? 2 : 4;
     const int kt = dtype == TC_DTYPE_BF16 ? 64 : 32;
     if (K % kt != 0) return TC_ERR_ARG;
