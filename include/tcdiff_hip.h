@@ -685,6 +685,26 @@ int tcdiff_loss_terms_bwd(const float* model_out, const float* x_start, const fl
 int tcdiff_fk_bwd(const float* motion, const float* d_joints, long n, int C, const int* parents, const float* offsets,
                   float* d_out, hipStream_t stream);
 
+/* ---- render-time pose export (csrc/export.hip) ----------------------------------------------------------------------
+ * The post-processing of GaussianDiffusion.render_sample (model/diffusion.py:811-988) up to the arrays it pickles:
+ * samples [b][S * dn][151] (row = frame * dn + dancer; 4 contacts, 3 root, 24 x 6 rotation) are clipped to [-1, 1] and
+ * un-normalised with the min-max scaler's scale_ / min_ [151] (dataset/preprocess.py:39-43, dataset/scaler.py:80-83), the
+ * rotations go 6-D -> axis-angle (dataset/quaternion.py:28-32), and SMPLSkeleton.forward (vis.py:358-406) gives the joints.
+ *   TC_EXPORT_NORMAL: every clip on its own; P = b * S * dn poses, pose p = sample row p; contact [P][4] is written.
+ *   TC_EXPORT_LONG:   b half-overlapping windows of one song stitched as model/diffusion.py:841-897 does: roots
+ *                     cross-faded (fade_out * p_i + fade_in * p_{i+1}), rotations slerped (dataset/quaternion.py:35-71)
+ *                     with weight linspace(0, 1, S / 2); P = (S + (b - 1) S / 2) * dn poses, frame-major / dancer-minor;
+ *                     S even; `fade` (DEVICE float [S]) holds torch.linspace(0, 1, S / 2) then torch.linspace(1, 0, S / 2)
+ *                     in float32; contact is not written (the reference drops contacts in this mode) and may be NULL.
+ * Outputs (DEVICE fp32): smpl_trans [P][3], smpl_poses [P][24][3] axis-angle, full_pose [P][24][3] joint positions.
+ * parents (HOST int[24], a parent precedes its children) / offsets (HOST float[24][3]) as tcdiff_smpl_fk.
+ * TC_ERR_ARG for a NULL pointer, b < 1, S < 1, dn < 1, an unknown mode, or a LONG job with an odd S. */
+#define TC_EXPORT_NORMAL 0
+#define TC_EXPORT_LONG 1
+int tcdiff_pose_export(const float* samples, int b, int S, int dn, int mode, const float* scale, const float* min_,
+                       const float* fade, const int* parents, const float* offsets, float* smpl_trans, float* smpl_poses,
+                       float* full_pose, float* contact, hipStream_t stream);
+
 /* library identification */
 const char* tcdiff_version(void);
 

@@ -15,6 +15,7 @@ EPI_STORE_T, EPI_STORE_F32, EPI_QKV_HEADS = 0, 1, 2
 ROW_BIAS, ROW_LN_POST, ROW_FILM, ROW_RES, ROW_STORE_X, ROW_NEXT_LN, ROW_STORE_H, ROW_STORE_ROT = \
     1, 2, 4, 8, 16, 32, 64, 128
 SAMPLER_DDPM, SAMPLER_DDIM = 0, 1
+EXPORT_NORMAL, EXPORT_LONG = 0, 1      # TC_EXPORT_* (tcdiff_pose_export)
 SAMPLER_ADVANCE = 0x100          # OR into the mode: sampler_update also advances counter[3] (step_prologue protocol)
 CHAIN_A, CHAIN_B, CHAIN_B_LAST, CHAIN_FULL, CHAIN_FULL_LAST, CHAIN_FRONT = 0, 1, 2, 3, 4, 5
 
@@ -152,6 +153,8 @@ _SIGS = {
     "tcdiff_loss_total": [_vp, _i, _vp, _vp],
     "tcdiff_loss_terms_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "tcdiff_fk_bwd": [_vp, _vp, _l, _i, C.POINTER(_i), C.POINTER(_f), _vp, _vp],
+    # render-time pose export (csrc/export.hip)
+    "tcdiff_pose_export": [_vp, _i, _i, _i, _i, _vp, _vp, _vp, C.POINTER(_i), C.POINTER(_f), _vp, _vp, _vp, _vp, _vp],
 }
 
 EXPORTS = sorted(list(_SIGS) + ["tcdiff_version"])

@@ -7,6 +7,7 @@
 // What it replaces (reference file:line):
 //   ax_from_6v                 dataset/quaternion.py:28-32 -> pytorch3d rotation_6d_to_matrix, matrix_to_axis_angle
 //   SMPLSkeleton.forward       vis.py:358-406 -> pytorch3d axis_angle_to_quaternion, quaternion_apply, quaternion_multiply
+//   quat_slerp                 dataset/quaternion.py:35-71 (the long-mode stitch of render_sample; csrc/export.hip)
 //   and torch autograd through both (model/diffusion.py:692-733 is differentiated by accelerator.backward, TCDiff.py:232).
 // The pytorch3d arithmetic (0.7.1, absent from the reference tree) is restated from its published definitions: real-first
 // quaternions, Gram-Schmidt rows b1 b2 b3, candidate quaternion with the largest component, small-angle series
@@ -111,6 +112,27 @@ TC_HD Q4 qmul_std(Q4 a, Q4 b) {
 TC_HD V3 qapply(Q4 q, V3 p) {
     const Q4 t = qmul_raw(qmul_raw(q, q4(0.0f, p.x, p.y, p.z)), qconj(q));
     return v3(t.x, t.y, t.z);
+}
+
+// dataset/quaternion.py:35-71 for one pair: y flipped when x . y < 0; the linear weights (1 - a, a) where 1 - |x . y| < 0.01,
+// else sin((1 - a) om) / sin om and sin(a om) / sin om with om = acos|x . y|.  The result is not renormalised (nor is the
+// reference's).
+TC_HD Q4 quat_slerp(Q4 x, Q4 y, float a) {
+    float d = x.w * y.w + x.x * y.x + x.y * y.y + x.z * y.z;
+    if (d < 0.0f) {
+        d = -d;
+        y = q4(-y.w, -y.x, -y.y, -y.z);
+    }
+    float a0, a1;
+    if (1.0f - d < 0.01f) {
+        a0 = 1.0f - a;
+        a1 = a;
+    } else {
+        const float om = acosf(d), so = sinf(om);
+        a0 = sinf((1.0f - a) * om) / so;
+        a1 = sinf(a * om) / so;
+    }
+    return q4(a0 * x.w + a1 * y.w, a0 * x.x + a1 * y.x, a0 * x.y + a1 * y.y, a0 * x.z + a1 * y.z);
 }
 
 struct FkSkel { int parent[TC_FK_J]; int has_children[TC_FK_J]; float off[TC_FK_J][3]; };

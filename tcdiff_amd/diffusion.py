@@ -713,13 +713,30 @@ class GaussianDiffusion(nn.Module):
     def forward(self, x, cond, t_override=None, trj_dist=None):
         return self.loss(x, cond, t_override, trj_dist=trj_dist)
 
-    # ---- render_sample: sampling only ---------------------------------------------------------------------
+    # ---- render_sample: sampling and the fk_out pose export ----------------------------------------------------------
     @torch.no_grad()
     def render_sample(self, shape, cond, normalizer=None, epoch=None, render_out=None, fk_out=None, name=None,
                       sound=True, mode="normal", noise=None, constraint=None, sound_folder="ood_sliced",
                       start_point=None, render=True, required_dancer_num=4, x_0=None, render_len=512):
-        """Mode dispatch of the reference (model/diffusion.py:784-806).  The post-processing that follows in the
-        reference (un-normalise, FK, matplotlib / ffmpeg, pickle) is out of scope: the samples are returned."""
+        """Mode dispatch of the reference (model/diffusion.py:784-806); a tensor ``shape`` is taken as the samples.
+
+        With a ``normalizer`` and an ``fk_out`` directory, the post-processing of model/diffusion.py:811-988 follows:
+        un-normalise, 6-D -> axis-angle, the window stitch in "long" mode, SMPL FK -- one HIP launch
+        (tcdiff_amd/export.py) -- and the reference's pickles: one ``{epoch}_{num}_{clip}.pkl`` per clip in "normal",
+        "inpaint" and "ctrl" mode, one ``{epoch}_{song}.pkl`` per song in "long" mode, each holding ``smpl_poses``,
+        ``smpl_trans`` and ``full_pose``.  The matplotlib / ffmpeg drawing (``skeleton_render``) is not built: nothing is
+        drawn, and ``render_out``, ``sound``, ``sound_folder``, ``render`` and ``render_len`` are unused.  The samples are
+        returned either way (the reference returns None)."""
+        samples = self._render_samples(shape, cond, mode, noise, constraint, start_point, x_0)
+        if normalizer is not None and fk_out is not None:
+            from .export import export_poses, write_fk_out
+            x = samples if samples.is_cuda else samples.to(self._device())
+            parents, offsets = self._skeleton(x.device)
+            q, pos, poses, _ = export_poses(x, normalizer, mode, required_dancer_num, parents=parents, offsets=offsets)
+            write_fk_out(fk_out, mode, epoch, name, q, pos, poses)
+        return samples
+
+    def _render_samples(self, shape, cond, mode, noise, constraint, start_point, x_0):
         if isinstance(shape, tuple):
             if mode == "inpaint":
                 fn = self.inpaint_loop

@@ -494,3 +494,11 @@ def fk_bwd(motion, d_joints, n, Cn, parents, offsets, d_out):
     par = (C.c_int * 24)(*[int(p) for p in parents])
     off = (C.c_float * 72)(*[float(v) for row in offsets for v in row])
     L.check(L.load().tcdiff_fk_bwd(_p(motion), _p(d_joints), n, Cn, par, off, _p(d_out), stream()), "tcdiff_fk_bwd")
+
+
+# ---- render-time pose export ---------------------------------------------------------------------------------------------
+def pose_export(samples, b, S, dn, mode, scale, min_, fade, parents, offsets, smpl_trans, smpl_poses, full_pose, contact):
+    par = (C.c_int * 24)(*[int(p) for p in parents])
+    off = (C.c_float * 72)(*[float(v) for row in offsets for v in row])
+    L.check(L.load().tcdiff_pose_export(_p(samples), b, S, dn, mode, _p(scale), _p(min_), _p(fade), par, off, _p(smpl_trans),
+                                        _p(smpl_poses), _p(full_pose), _p(contact), stream()), "tcdiff_pose_export")

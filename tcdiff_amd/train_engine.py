@@ -284,8 +284,10 @@ class TrainEngine:
         c = model.engine_config()
         if c["latent"] != 512 or c["n_head"] * 64 != 512:
             raise L.TcdiffError(f"latent_dim={c['latent']}, num_heads={c['n_head']}: the gfx950 kernels are built for the width the "
-                                "reference instantiates, latent_dim=512 as 8 heads x 64 (TCDiff.py:76-87); the constructor's own "
-                                "defaults (256 / 4, model/model.py:417-431) and any other width are not built")
+                                "reference instantiates, latent_dim=512 as 8 heads x 64 (TCDiff.py:76-87).  The reference itself "
+                                "fails at other widths: traj_Modulation's ConcatSquashLinear expects a 512-wide context "
+                                "(model/model.py:256,301-303) and is fed one of latent_dim (:353), so its constructor defaults "
+                                "(256 / 4, model/model.py:417-431) raise inside the reference too")
         self.H, self.NL, self.S, self.dn, self.nf, self.ff = c["n_head"], c["n_layers"], c["seq_len"], c["dn"], \
             c["nfeats"], c["ff"]
         self.Cd = c["cond_dim"]
