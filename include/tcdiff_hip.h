@@ -705,6 +705,58 @@ int tcdiff_pose_export(const float* samples, int b, int S, int dn, int mode, con
                        const float* fade, const int* parents, const float* offsets, float* smpl_trans, float* smpl_poses,
                        float* full_pose, float* contact, hipStream_t stream);
 
+/* ---- Dance-Beat Navigator (csrc/navigator.hip) -----------------------------------------------------------------------
+ * TrajDecoder (TrajDecoder/model/traj_model.py:125-200: latent_dim 64, 4 heads, nfeats 2) and the sliding-window rollout of
+ * TCDiff.test_loop (TCDiff.py:526-547), exact fp32 throughout (v_mfma_f32_16x16x4_f32 products).  All pointers DEVICE fp32.
+ *
+ * The music front: `music_projection` (traj_model.py:142-148,177-184: frames paired to 876 features, 876 -> 438 -> 438 -> 64
+ * with LeakyReLU(0.01)) and `cond_emb` (:79,109) of EVERY frame pair of cond [b][n_frames][438] (an odd last frame is
+ * dropped), once per rollout: mp [b][n_frames / 2][64] = music_projection, me [same] = cond_emb(mp).  A window that starts at
+ * the even frame `start` reads rows start / 2 ... of both.  wm: the packed weights, zero-padded to K = 880 / N = 448:
+ * W1 [448][880], b1 [448], W2 [448][448], b2 [448], W3 [64][448], b3 [64], Wc [64][64], bc [64] (628736 floats). */
+int tcdiff_nav_music_front(const float* cond, int b, int n_frames, const float* wm, float* mp, float* me, hipStream_t stream);
+
+typedef struct {
+    int b, dn, seq;      /* clips, dancers, frames per window: T = dn * seq <= 500 token rows per clip */
+    int n_layers;        /* transformer blocks */
+    int pairs;           /* rows per clip of me / mp */
+    int me_off, mp_off;  /* window 0: first row of the conditioning side (music_feat[:, :seq]) / of the prediction side
+                            (music_feat[:, -seq:], traj_model.py:187,190) */
+    int win_stride;      /* added to both per window (= step) */
+    int step;            /* frames appended to `roll` per window */
+    int roll_frames, roll_off; /* frames per (clip, dancer) of `roll`; window w's tail goes to frame roll_off + w * step */
+    const float* lstm_w;   /* [3][128][256]: k < 64 weight_ih_l (zero beyond the layer's input width), k >= 64 weight_hh_l,
+                              transposed; gate rows in PyTorch's order i, f, g, o */
+    const float* lstm_bih; /* [3][256] */
+    const float* lstm_bhh; /* [3][256] */
+    const float* pe;       /* [500][64] PositionalEncoding rows (model/utils.py:18-25) */
+    const float* blocks;   /* [n_layers][198272]: ln1 g, b; Wq, bq; Wk, bk; Wv, bv; Wproj, b; ln2 g, b; W1 [512][128], b1;
+                              W2 [128][512], b2 -- every W as nn.Linear stores it, [out][in] */
+    const float* dec;      /* Decoder (traj_model.py:159-167): W1 [128][192], b1, W2 [128][128], b2, W3 [64][128], b3,
+                              W4 [16][64] (rows 2.. zero), b4 [16]: 50512 floats */
+    const float* me;       /* tcdiff_nav_music_front's tables */
+    const float* mp;
+    float* traj;           /* [b][T][2]: in = the conditioning window, out = the prediction (the next window's input) */
+    float* lstm_out;       /* [b][T][64] workspace */
+    float* x;              /* [b][T][128] workspace (residual stream) */
+    float* q;              /* [2][b][Tp][128] workspaces, Tp = T rounded up to 16; ZERO before the first call (the pad rows */
+    float* k;              /* [2][b][4][Tp][32]   / columns are read and never written)                                  */
+    float* vt;             /* [2][b][4][32][Tp] */
+    float* roll;           /* [b][dn][roll_frames][2] or NULL */
+    float* tap_lstm;       /* NULL, or [b][T][64]: window 0's LSTM output before the positional encoding */
+    float* tap_blocks;     /* NULL, or [n_layers][b][T][128]: window 0's residual stream after every block */
+} tcdiff_nav_args;
+
+/* n_windows forwards of TrajDecoder chained as TCDiff.py:540-544 chains them: per window one LSTM launch (traj_model.py:139,174
+ * -- built without batch_first, so the recurrence runs over the CLIP index b and the T positions are its batch; the epilogue
+ * adds the PositionalEncoding row, :106), one front launch ([cond_emb rows repeated dn times | LSTM rows], :109-118, block 0's
+ * LN1 + Q / K / V) and one launch per block (:29-46,62-65: attention WITHOUT mask, heads of 32, proj + residual, LN2, MLP with
+ * erf-GELU, residual, the next block's LN1 + Q / K / V; the last one runs the Decoder on [x | prediction-side music rows],
+ * :190-200, writes `traj` and the last `step` frames of every dancer to `roll`): n_layers + 2 launches per window, one stream.
+ * n_windows = 1 with me_off = 0, mp_off = pairs - seq and roll = NULL is TrajDecoder.forward.
+ * TC_ERR_UNSUPPORTED for T > 500 (PositionalEncoding's max_len: the reference raises there too). */
+int tcdiff_nav_rollout(const tcdiff_nav_args* a, int n_windows, hipStream_t stream);
+
 /* library identification */
 const char* tcdiff_version(void);
 

@@ -95,6 +95,15 @@ ROWF_BIAS, ROWF_DROP_PRE, ROWF_LN_POST, ROWF_DROP_POST, ROWF_FILM, ROWF_RES, ROW
     ROWF_STORE_ROT = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512
 
 
+class NavArgs(C.Structure):
+    """tcdiff_nav_args (include/tcdiff_hip.h): one Dance-Beat Navigator rollout."""
+    _fields_ = [("b", _i), ("dn", _i), ("seq", _i), ("n_layers", _i), ("pairs", _i), ("me_off", _i), ("mp_off", _i),
+                ("win_stride", _i), ("step", _i), ("roll_frames", _i), ("roll_off", _i), ("lstm_w", _vp), ("lstm_bih", _vp),
+                ("lstm_bhh", _vp), ("pe", _vp), ("blocks", _vp), ("dec", _vp), ("me", _vp), ("mp", _vp), ("traj", _vp),
+                ("lstm_out", _vp), ("x", _vp), ("q", _vp), ("k", _vp), ("vt", _vp), ("roll", _vp), ("tap_lstm", _vp),
+                ("tap_blocks", _vp)]
+
+
 class AdanScalars(C.Structure):
     _fields_ = [(n, _f) for n in ("b1", "omb1", "b2", "omb2", "b3", "omb3", "cm", "cv", "cn", "eps", "lr", "denom")] + \
         [("first", _i)]
@@ -155,6 +164,9 @@ _SIGS = {
     "tcdiff_fk_bwd": [_vp, _vp, _l, _i, C.POINTER(_i), C.POINTER(_f), _vp, _vp],
     # render-time pose export (csrc/export.hip)
     "tcdiff_pose_export": [_vp, _i, _i, _i, _i, _vp, _vp, _vp, C.POINTER(_i), C.POINTER(_f), _vp, _vp, _vp, _vp, _vp],
+    # Dance-Beat Navigator (csrc/navigator.hip)
+    "tcdiff_nav_music_front": [_vp, _i, _i, _vp, _vp, _vp, _vp],
+    "tcdiff_nav_rollout": [C.POINTER(NavArgs), _i, _vp],
 }
 
 EXPORTS = sorted(list(_SIGS) + ["tcdiff_version"])

@@ -1,0 +1,276 @@
+"""The Dance-Beat Navigator on the MI355X: `TrajDecoder` (TrajDecoder/model/traj_model.py:125-200) and the sliding-window
+rollout of `TCDiff.test_loop` (TCDiff.py:526-547), as HIP kernels (csrc/navigator.hip), inference only.
+
+    traj_model = TrajDecoder(nfeats=2, trans_layer=6, window_size=100)
+    traj_model.load_state_dict(ckpt["net"], strict=True)                 # the reference's checkpoint, key for key
+    traj_model.cuda().eval()
+    x_traj = rollout(traj_model, x[:, :, :, [4, 5]], cond, step=25)      # (b, dn, window + n_windows * step, 2)
+    x_0 = tcdiff_amd.io.x0_from_navigator(x_traj)                        # Kalman smoothing, zero z, frame-major
+
+What the module computes, restated (everything fp32, eval-mode dropouts are identities):
+
+* `lstm`: 3-layer `nn.LSTM(2 -> 64)` on x reshaped to (b, dn * seq, 2).  The reference builds it WITHOUT `batch_first`, so
+  **the recurrence runs over the clip index b** and the dn * seq positions are its independent batch: clip i's output depends
+  on clips 0 .. i - 1 (one clip alone and the same clip inside a batch differ by ~1e-3).  The checkpoint was trained that
+  way; the kernel reproduces it.
+* `music_projection`: frames paired to (b, n // 2, 876) (an odd last frame dropped), 876 -> 438 -> 438 -> 64 with
+  LeakyReLU(0.01).
+* `trans_extractor`: PositionalEncoding rows 0 .. dn * seq - 1 added to the LSTM output (max_len 500: more positions raise, as
+  in the reference), [cond_emb(music[:, :seq]) repeated dn times | that] -> width 128, `trans_layer` pre-norm blocks: Q / K / V
+  with biases, 4 heads of 32, scale 1 / sqrt(32), **no mask** (the `attn.mask` buffers are registered and never read), proj,
+  MLP 128 -> 512 -> 128 with the erf GELU.  `traj_emb` is a parameter forward never uses.  Both are kept for the state_dict.
+* `Decoder`: [features | music[:, -seq:] repeated dn times] (192) -> 128 -> 128 -> 64 -> 2 with LeakyReLU, back to
+  (b, dn, seq, 2).
+
+`rollout` hoists the music front: window starts are even, so a window's frame pairs are pairs of the whole `cond`; the two
+tables are computed once for all cond_len // 2 pairs and every window reads its rows.  A row of the kernel's products depends
+on its own input row only, so hoisting changes no bits.
+"""
+import ctypes as C
+import math
+
+import torch
+import torch.nn as nn
+
+from . import _lib as L
+from . import kernels as K
+
+MAX_POS = 500                      # PositionalEncoding max_len (model/utils.py:12)
+_BK, _DC, _MU = 198272, 50512, 628736          # packed sizes (csrc/navigator.hip)
+
+
+class _PositionalEncoding(nn.Module):
+    def __init__(self, d_model, dropout, max_len=MAX_POS):
+        super().__init__()
+        self.dropout = nn.Dropout(dropout)
+        pos = torch.arange(0, max_len).unsqueeze(1)
+        div = torch.exp(torch.arange(0, d_model, 2) * (-math.log(10000.0) / d_model))
+        pe = torch.zeros(max_len, d_model)
+        pe[:, 0::2] = torch.sin(pos * div)
+        pe[:, 1::2] = torch.cos(pos * div)
+        self.register_buffer("pe", pe.unsqueeze(1))          # (max_len, 1, d_model)
+
+
+class _Attention(nn.Module):
+    def __init__(self, dim, block_size, dropout):
+        super().__init__()
+        self.key = nn.Linear(dim, dim)
+        self.query = nn.Linear(dim, dim)
+        self.value = nn.Linear(dim, dim)
+        self.attn_drop = nn.Dropout(dropout)
+        self.resid_drop = nn.Dropout(dropout)
+        self.proj = nn.Linear(dim, dim)
+        # part of the reference's state_dict; its forward never applies it
+        self.register_buffer("mask", torch.tril(torch.ones(block_size, block_size)).view(1, 1, block_size, block_size))
+
+
+class _Block(nn.Module):
+    def __init__(self, dim, block_size, dropout):
+        super().__init__()
+        self.ln1 = nn.LayerNorm(dim)
+        self.ln2 = nn.LayerNorm(dim)
+        self.attn = _Attention(dim, block_size, dropout)
+        self.mlp = nn.Sequential(nn.Linear(dim, 4 * dim), nn.GELU(), nn.Linear(4 * dim, dim), nn.Dropout(dropout))
+
+
+class _Extractor(nn.Module):
+    def __init__(self, dim, block_size, layers, dropout):
+        super().__init__()
+        self.cond_emb = nn.Linear(dim, dim)
+        self.traj_emb = nn.Linear(3, dim)                    # unused by forward, in the checkpoint
+        self.drop = nn.Dropout(dropout)
+        self.blocks = nn.Sequential(*[_Block(2 * dim, block_size, dropout) for _ in range(layers)])
+        self.pos_embed = _PositionalEncoding(dim, dropout)
+        for m in self.modules():                             # the reference's initialisation of this sub-tree
+            if isinstance(m, nn.Linear):
+                m.weight.data.normal_(mean=0.0, std=0.02)
+                m.bias.data.zero_()
+
+
+class TrajDecoder(nn.Module):
+    """Drop-in for `TrajDecoder.model.traj_model.TrajDecoder`: the same constructor, the same 133 state_dict entries (shapes and
+    order, incl. `lstm.*_l{0,1,2}`, the `attn.mask` buffers, `trans_extractor.pos_embed.pe`, `trans_extractor.traj_emb.*`), and
+    `forward(x (b, dn, seq, 2), music_feat (b, n, 438)) -> (b, dn, seq, 2)` on a HIP device.  Note the LSTM recurrence over the
+    clip axis (module docstring): results depend on which clips share a batch, exactly as in the reference.  Inference only."""
+
+    def __init__(self, nfeats, trans_layer=4, window_size=60, latent_dim: int = 64, dropout: float = 0.1, n_head: int = 4,
+                 cond_feature_dim: int = 438):
+        super().__init__()
+        if nfeats != 2 or latent_dim != 64 or n_head != 4 or cond_feature_dim != 438:
+            raise L.TcdiffError("TrajDecoder: the kernels are built for nfeats=2, latent_dim=64, n_head=4, cond_feature_dim=438 "
+                                f"(got {nfeats}, {latent_dim}, {n_head}, {cond_feature_dim})")
+        if trans_layer < 1:
+            raise L.TcdiffError("TrajDecoder: trans_layer must be at least 1")
+        self.latent_dim, self.window_size, self.trans_layer = latent_dim, window_size, trans_layer
+        self.lstm = nn.LSTM(input_size=nfeats, hidden_size=latent_dim, num_layers=3)
+        self.music_projection = nn.Sequential(nn.Linear(cond_feature_dim * 2, cond_feature_dim), nn.LeakyReLU(),
+                                              nn.Linear(cond_feature_dim, cond_feature_dim), nn.LeakyReLU(),
+                                              nn.Linear(cond_feature_dim, latent_dim))
+        self.trans_extractor = _Extractor(latent_dim, window_size, trans_layer, dropout)
+        self.Decoder = nn.Sequential(nn.Linear(latent_dim * 3, latent_dim * 2), nn.LeakyReLU(),
+                                     nn.Linear(latent_dim * 2, latent_dim * 2), nn.LeakyReLU(),
+                                     nn.Linear(latent_dim * 2, latent_dim), nn.LeakyReLU(), nn.Linear(latent_dim, nfeats))
+        self.__dict__["_packed"] = None
+        self.__dict__["_plans"] = {}
+        super().train(False)
+
+    def train(self, mode: bool = True):
+        if mode:
+            raise L.TcdiffError("TrajDecoder is inference only: training the Navigator (TrajDecoder/train_traj.py) is not built")
+        return super().train(False)
+
+    # ---- weights ------------------------------------------------------------------------------------------------------------------
+    def _weights_version(self):
+        ts = list(self.parameters()) + [self.trans_extractor.pos_embed.pe]
+        return tuple(t._version for t in ts) + (tuple(map(id, ts)), str(ts[0].device))
+
+    def _weights(self):
+        """The packed device weights, rebuilt whenever a parameter changed in place or was replaced (as engine.py does)."""
+        ver = self._weights_version()
+        pk = self.__dict__["_packed"]
+        if pk is not None and pk["version"] == ver:
+            return pk
+        f = lambda t: t.detach().to(torch.float32)
+        dev = self.lstm.weight_ih_l0.device
+        with torch.no_grad():
+            lw = torch.zeros(3, 128, 256, device=dev)
+            for l in range(3):
+                wi = f(getattr(self.lstm, f"weight_ih_l{l}"))
+                lw[l, :wi.shape[1]] = wi.t()
+                lw[l, 64:] = f(getattr(self.lstm, f"weight_hh_l{l}")).t()
+            bih = torch.stack([f(getattr(self.lstm, f"bias_ih_l{l}")) for l in range(3)]).contiguous()
+            bhh = torch.stack([f(getattr(self.lstm, f"bias_hh_l{l}")) for l in range(3)]).contiguous()
+            parts = []
+            for blk in self.trans_extractor.blocks:
+                a = blk.attn
+                for t in (blk.ln1.weight, blk.ln1.bias, a.query.weight, a.query.bias, a.key.weight, a.key.bias, a.value.weight,
+                          a.value.bias, a.proj.weight, a.proj.bias, blk.ln2.weight, blk.ln2.bias, blk.mlp[0].weight, blk.mlp[0].bias,
+                          blk.mlp[2].weight, blk.mlp[2].bias):
+                    parts.append(f(t).reshape(-1))
+            blocks = torch.cat(parts).contiguous()
+            d = self.Decoder
+            w4, b4 = torch.zeros(16, 64, device=dev), torch.zeros(16, device=dev)
+            w4[:2], b4[:2] = f(d[6].weight), f(d[6].bias)
+            dec = torch.cat([f(t).reshape(-1) for t in (d[0].weight, d[0].bias, d[2].weight, d[2].bias, d[4].weight, d[4].bias)] +
+                            [w4.reshape(-1), b4]).contiguous()
+            m = self.music_projection
+            w1, b1 = torch.zeros(448, 880, device=dev), torch.zeros(448, device=dev)
+            w2, b2 = torch.zeros(448, 448, device=dev), torch.zeros(448, device=dev)
+            w3 = torch.zeros(64, 448, device=dev)
+            w1[:438, :876], b1[:438] = f(m[0].weight), f(m[0].bias)
+            w2[:438, :438], b2[:438] = f(m[2].weight), f(m[2].bias)
+            w3[:, :438] = f(m[4].weight)
+            ce = self.trans_extractor.cond_emb
+            mus = torch.cat([t.reshape(-1) for t in (w1, b1, w2, b2, w3, f(m[4].bias), f(ce.weight), f(ce.bias))]).contiguous()
+            pe = f(self.trans_extractor.pos_embed.pe).reshape(MAX_POS, 64).contiguous()
+        assert blocks.numel() == self.trans_layer * _BK and dec.numel() == _DC and mus.numel() == _MU
+        pk = dict(version=ver, lstm_w=lw, bih=bih, bhh=bhh, blocks=blocks, dec=dec, music=mus, pe=pe)
+        self.__dict__["_packed"] = pk
+        return pk
+
+    # ---- workspaces ---------------------------------------------------------------------------------------------------------------
+    def _plan(self, dev, b, dn, seq, pairs, roll_frames, taps):
+        key = (str(dev), b, dn, seq, pairs, roll_frames, bool(taps))
+        pl = self.__dict__["_plans"].get(key)
+        if pl is None:
+            T = dn * seq
+            Tp = K.round_up(T, 16)
+            z = lambda *s: torch.zeros(*s, device=dev, dtype=torch.float32)
+            pl = dict(traj=z(b, T, 2), lstm_out=z(b, T, 64), x=z(b, T, 128), q=z(2, b, Tp, 128), k=z(2, b, 4, Tp, 32),
+                      vt=z(2, b, 4, 32, Tp), mp=z(b, pairs, 64), me=z(b, pairs, 64),
+                      roll=z(b, dn, roll_frames, 2) if roll_frames else None,
+                      tap_lstm=z(b, T, 64) if taps else None, tap_blocks=z(self.trans_layer, b, T, 128) if taps else None)
+            if len(self.__dict__["_plans"]) >= 4:
+                self.__dict__["_plans"].clear()
+            self.__dict__["_plans"][key] = pl
+        return pl
+
+    def _check(self, x, music):
+        if self.training:
+            raise L.TcdiffError("TrajDecoder is inference only: training the Navigator (TrajDecoder/train_traj.py) is not built")
+        if torch.is_grad_enabled() and (x.requires_grad or music.requires_grad):
+            raise L.TcdiffError("TrajDecoder: inputs that require grad need the Navigator's training step "
+                                "(TrajDecoder/train_traj.py), which is not built")
+        dev = self.lstm.weight_ih_l0.device
+        if dev.type != "cuda" or x.device != dev or music.device != dev:
+            raise L.TcdiffError("TrajDecoder runs on MI355X only: move the module and its inputs to cuda (no CPU fallback)")
+        if x.dim() != 4 or x.shape[-1] != 2:
+            raise L.TcdiffError(f"TrajDecoder: x must be (b, dn, seq, 2), got {tuple(x.shape)}")
+        if music.dim() != 3 or music.shape[-1] != 438 or music.shape[0] != x.shape[0]:
+            raise L.TcdiffError(f"TrajDecoder: music_feat must be ({x.shape[0]}, n, 438), got {tuple(music.shape)}")
+        if x.shape[1] * x.shape[2] > MAX_POS:
+            raise L.TcdiffError(f"TrajDecoder: dn * seq = {x.shape[1] * x.shape[2]} positions exceed PositionalEncoding's max_len "
+                                f"{MAX_POS} (the reference raises here too)")
+        if min(x.shape) < 1:
+            raise L.TcdiffError(f"TrajDecoder: empty input {tuple(x.shape)}")
+        return dev
+
+    def _launch(self, pl, wt, cond, b, dn, seq, pairs, n_windows, me_off, mp_off, stride, step, roll_off):
+        lib, st = L.load(), K.stream()
+        L.check(lib.tcdiff_nav_music_front(K._p(cond), b, cond.shape[1], K._p(wt["music"]), K._p(pl["mp"]), K._p(pl["me"]), st),
+                "tcdiff_nav_music_front")
+        roll = pl["roll"]
+        a = L.NavArgs(b=b, dn=dn, seq=seq, n_layers=self.trans_layer, pairs=pairs, me_off=me_off, mp_off=mp_off, win_stride=stride,
+                      step=step, roll_frames=0 if roll is None else roll.shape[2], roll_off=roll_off, lstm_w=K._p(wt["lstm_w"]),
+                      lstm_bih=K._p(wt["bih"]), lstm_bhh=K._p(wt["bhh"]), pe=K._p(wt["pe"]), blocks=K._p(wt["blocks"]),
+                      dec=K._p(wt["dec"]), me=K._p(pl["me"]), mp=K._p(pl["mp"]), traj=K._p(pl["traj"]),
+                      lstm_out=K._p(pl["lstm_out"]), x=K._p(pl["x"]), q=K._p(pl["q"]), k=K._p(pl["k"]), vt=K._p(pl["vt"]),
+                      roll=K._p(roll), tap_lstm=K._p(pl["tap_lstm"]), tap_blocks=K._p(pl["tap_blocks"]))
+        L.check(lib.tcdiff_nav_rollout(C.byref(a), n_windows, st), "tcdiff_nav_rollout")
+
+    @staticmethod
+    def _fill_taps(taps, pl, b, pairs):
+        taps["lstm"] = pl["tap_lstm"].clone()
+        taps["music"] = pl["mp"].clone()
+        taps["cond_emb"] = pl["me"].clone()
+        taps["blocks"] = pl["tap_blocks"].clone()
+
+    def forward(self, x, music_feat, taps=None):
+        """One window: `taps` (a dict, tests) receives the LSTM output, the projected music rows and every block's output."""
+        dev = self._check(x, music_feat)
+        b, dn, seq, _ = x.shape
+        pairs = music_feat.shape[1] // 2
+        if pairs < seq:
+            raise L.TcdiffError(f"TrajDecoder: {music_feat.shape[1]} music frames give {pairs} pairs, fewer than seq = {seq}")
+        wt = self._weights()
+        pl = self._plan(dev, b, dn, seq, pairs, 0, taps is not None)
+        cond = music_feat.detach().to(torch.float32).contiguous()
+        pl["traj"].copy_(x.detach().reshape(b, dn * seq, 2))
+        self._launch(pl, wt, cond, b, dn, seq, pairs, 1, 0, pairs - seq, 0, 0, 0)
+        if taps is not None:
+            self._fill_taps(taps, pl, b, pairs)
+        return pl["traj"].reshape(b, dn, seq, 2).clone()
+
+
+def window_starts(cond_len: int, window: int, step: int):
+    """The music-frame offsets of the rollout's windows (TCDiff.py:540)."""
+    return range(0, cond_len + 1 - (window + step) * 2, step * 2)
+
+
+def rollout(model: TrajDecoder, x_traj_xy, cond, step: int = 25, taps=None):
+    """TCDiff.py:526-547: `x_traj_xy` (b, dn, frames >= window, 2) gives the first window; every window of (window + step) * 2
+    music frames, moved by step * 2, predicts the next window from the previous one and contributes its last `step` frames.
+    Returns (b, dn, window + n_windows * step, 2) on the device; a `cond` too short for one window returns the initial window (the
+    reference's empty range).  The music front runs once for the whole `cond`; between the first and the last launch there is no
+    torch op, no allocation and no host synchronisation."""
+    window = model.window_size
+    if step < 1 or step > window:
+        raise L.TcdiffError(f"rollout: step must be in 1 .. window_size = {window}, got {step}")
+    if x_traj_xy.dim() != 4 or x_traj_xy.shape[2] < window:
+        raise L.TcdiffError(f"rollout: x_traj_xy must be (b, dn, >= {window} frames, 2), got {tuple(x_traj_xy.shape)}")
+    first = x_traj_xy[:, :, :window]
+    dev = model._check(first, cond)
+    b, dn = first.shape[:2]
+    n_windows = len(window_starts(cond.shape[1], window, step))
+    if n_windows == 0:
+        return first.detach().to(torch.float32).clone()
+    pairs = cond.shape[1] // 2
+    wt = model._weights()
+    pl = model._plan(dev, b, dn, window, pairs, window + n_windows * step, taps is not None)
+    condc = cond.detach().to(torch.float32).contiguous()
+    pl["traj"].copy_(first.detach().reshape(b, dn * window, 2))
+    pl["roll"][:, :, :window].copy_(first.detach())
+    model._launch(pl, wt, condc, b, dn, window, pairs, n_windows, 0, step, step, step, window)
+    if taps is not None:
+        model._fill_taps(taps, pl, b, pairs)
+    return pl["roll"].clone()
