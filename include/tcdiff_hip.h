@@ -705,6 +705,27 @@ int tcdiff_pose_export(const float* samples, int b, int S, int dn, int mode, con
                        const float* fade, const int* parents, const float* offsets, float* smpl_trans, float* smpl_poses,
                        float* full_pose, float* contact, hipStream_t stream);
 
+/* ---- motion ingest (csrc/ingest.hip) -----------------------------------------------------------------------------------
+ * The motion side of AIOZDataset.process_dataset (dataset/group_dataset.py:167-238), the inverse of tcdiff_pose_export:
+ * pos [clips][dn][sq][3] root positions and q [clips][dn][sq][72] axis-angle rotations (DEVICE fp32, Y-up, never written)
+ * -> feats [clips][dn][sq][151] = [contacts 4 | root 3 | 6-D 24 x 6], normalised to [-1, 1].  Two launches, no host
+ * synchronisation, for any number of clips:
+ *   per pose: joint 0's rotation with 90 degrees about x on the left (:184-191), the root position rotated the same way
+ *             (:195-198), SMPLSkeleton.forward (:201, vis.py:358-406), ax_to_6v of all 24 joints (:210,
+ *             dataset/quaternion.py:21-25), the four foot joints to `feet` [clips * dn * sq][4][3] (workspace);
+ *   per clip: contacts = |feet[t + 1] - feet[t]| < 0.01 along one dancer's frames, 1 on the last frame (:204-207);
+ *             fit != 0: a Normalizer fitted on THIS clip's dn * sq rows (:217-218, dataset/scaler.py:50-70) -- stats
+ *                       [clips][4][151] receives data_min_, data_max_, scale_ = 2 / range (range < 10 eps -> 1) and
+ *                       min_ = -1 - data_min_ * scale_; scale / min_ are not read;
+ *             fit == 0: scale / min_ (DEVICE float [151]) are used for every clip (:219-220); stats is not written;
+ *             then x * scale_ + min_ as two rounded operations, clipped to [-1, 1] (:221, dataset/scaler.py:73-78).
+ * raw (optional, as feats): the un-normalised features.  parents / offsets as tcdiff_smpl_fk.
+ * TC_ERR_ARG for a NULL pointer (raw excepted; stats / scale / min_ as the mode needs them), clips, dn or sq < 1, or a
+ * parent that does not precede its child. */
+int tcdiff_motion_ingest(const float* pos, const float* q, int clips, int dn, int sq, const int* parents, const float* offsets,
+                         int fit, const float* scale, const float* min_, float* feats, float* raw, float* feet, float* stats,
+                         hipStream_t stream);
+
 /* ---- Dance-Beat Navigator (csrc/navigator.hip) -----------------------------------------------------------------------
  * TrajDecoder (TrajDecoder/model/traj_model.py:125-200: latent_dim 64, 4 heads, nfeats 2) and the sliding-window rollout of
  * TCDiff.test_loop (TCDiff.py:526-547), exact fp32 throughout (v_mfma_f32_16x16x4_f32 products).  All pointers DEVICE fp32.

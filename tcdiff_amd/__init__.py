@@ -1,11 +1,14 @@
 """tcdiff_amd: MI355X-native (gfx950) implementation of TCDiff's denoising hot path.
 
     from tcdiff_amd import DanceDecoder, GaussianDiffusion     # drop-ins for model.model / model.diffusion
+    from tcdiff_amd import AIOZDataset                         # drop-in for dataset.group_dataset
 """
 from .model import DanceDecoder  # noqa: F401
 from .diffusion import GaussianDiffusion, EMA  # noqa: F401
 from .adan import Adan  # noqa: F401
 from .fk import SMPLSkeleton, ax_from_6v  # noqa: F401
 from .navigator import TrajDecoder  # noqa: F401
+from .dataset import AIOZDataset, process_motion  # noqa: F401
 
-__all__ = ["DanceDecoder", "GaussianDiffusion", "EMA", "Adan", "SMPLSkeleton", "ax_from_6v", "TrajDecoder"]
+__all__ = ["DanceDecoder", "GaussianDiffusion", "EMA", "Adan", "SMPLSkeleton", "ax_from_6v", "TrajDecoder", "AIOZDataset",
+           "process_motion"]

@@ -164,6 +164,8 @@ _SIGS = {
     "tcdiff_fk_bwd": [_vp, _vp, _l, _i, C.POINTER(_i), C.POINTER(_f), _vp, _vp],
     # render-time pose export (csrc/export.hip)
     "tcdiff_pose_export": [_vp, _i, _i, _i, _i, _vp, _vp, _vp, C.POINTER(_i), C.POINTER(_f), _vp, _vp, _vp, _vp, _vp],
+    # motion ingest (csrc/ingest.hip)
+    "tcdiff_motion_ingest": [_vp, _vp, _i, _i, _i, C.POINTER(_i), C.POINTER(_f), _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     # Dance-Beat Navigator (csrc/navigator.hip)
     "tcdiff_nav_music_front": [_vp, _i, _i, _vp, _vp, _vp, _vp],
     "tcdiff_nav_rollout": [C.POINTER(NavArgs), _i, _vp],

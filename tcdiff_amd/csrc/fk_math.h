@@ -135,6 +135,36 @@ TC_HD Q4 quat_slerp(Q4 x, Q4 y, float a) {
     return q4(a0 * x.w + a1 * y.w, a0 * x.x + a1 * y.x, a0 * x.y + a1 * y.y, a0 * x.z + a1 * y.z);
 }
 
+// ---- motion ingest (csrc/ingest.hip; reference dataset/group_dataset.py:183-210) ---------------------------------------
+// The first two rows of pytorch3d 0.7.1's quaternion_to_matrix, i.e. ax_to_6v's matrix_to_rotation_6d(axis_angle_to_matrix)
+// once the axis-angle is a quaternion: two_s = 2 / (q . q), the quaternion is NOT assumed to be of unit length.
+TC_HD void rot6_from_quat(Q4 q, float* d6) {
+    const float two_s = 2.0f / (q.w * q.w + q.x * q.x + q.y * q.y + q.z * q.z);
+    d6[0] = 1.0f - two_s * (q.y * q.y + q.z * q.z);
+    d6[1] = two_s * (q.x * q.y - q.z * q.w);
+    d6[2] = two_s * (q.x * q.z + q.y * q.w);
+    d6[3] = two_s * (q.x * q.y + q.z * q.w);
+    d6[4] = 1.0f - two_s * (q.x * q.x + q.z * q.z);
+    d6[5] = two_s * (q.y * q.z - q.x * q.w);
+}
+// group_dataset.py:184-191: the root's axis-angle with 90 degrees about x multiplied on the LEFT.  The constant is the
+// float32 value of the literal 0.7071068 as the reference writes it, not renormalised; quaternion_multiply standardises
+// the product to w >= 0.
+TC_HD V3 root_yup_to_zup(V3 aa) {
+    return axis_angle_from_quat(qmul_std(q4(0.7071068f, 0.7071068f, 0.0f, 0.0f), quat_from_axis_angle(aa)));
+}
+// group_dataset.py:195-198: RotateAxisAngle(90, "X", degrees=True).transform_points -- y' = c y - s z, z' = s y + c z with
+// c, s the float32 cosine and sine of float32(pi / 2) (c = -4.3711388e-08, not 0): two rounded products and a rounded sum.
+#define TC_ROTX90_COS (-4.37113883e-08f)
+#define TC_ROTX90_SIN (1.0f)
+TC_HD V3 rotate_x90(V3 p) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const float cy = TC_ROTX90_COS * p.y, sz = TC_ROTX90_SIN * p.z, sy = TC_ROTX90_SIN * p.y, cz = TC_ROTX90_COS * p.z;
+    return v3(p.x, cy - sz, sy + cz);
+}
+
 struct FkSkel { int parent[TC_FK_J]; int has_children[TC_FK_J]; float off[TC_FK_J][3]; };
 
 // joints[j] = world position of joint j; rw (optional, [24]) receives the world rotations the chain used

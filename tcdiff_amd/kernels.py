@@ -502,3 +502,11 @@ def pose_export(samples, b, S, dn, mode, scale, min_, fade, parents, offsets, sm
     off = (C.c_float * 72)(*[float(v) for row in offsets for v in row])
     L.check(L.load().tcdiff_pose_export(_p(samples), b, S, dn, mode, _p(scale), _p(min_), _p(fade), par, off, _p(smpl_trans),
                                         _p(smpl_poses), _p(full_pose), _p(contact), stream()), "tcdiff_pose_export")
+
+
+# ---- motion ingest -------------------------------------------------------------------------------------------------------
+def motion_ingest(pos, q, clips, dn, sq, parents, offsets, fit, scale, min_, feats, raw, feet, stats):
+    par = (C.c_int * 24)(*[int(p) for p in parents])
+    off = (C.c_float * 72)(*[float(v) for row in offsets for v in row])
+    L.check(L.load().tcdiff_motion_ingest(_p(pos), _p(q), clips, dn, sq, par, off, int(bool(fit)), _p(scale), _p(min_), _p(feats),
+                                          _p(raw), _p(feet), _p(stats), stream()), "tcdiff_motion_ingest")
