@@ -778,6 +778,90 @@ typedef struct {
  * TC_ERR_UNSUPPORTED for T > 500 (PositionalEncoding's max_len: the reference raises there too). */
 int tcdiff_nav_rollout(const tcdiff_nav_args* a, int n_windows, hipStream_t stream);
 
+/* ---- training the Navigator (csrc/navigator.hip train-mode forward, csrc/navigator_train.hip backward) ----------------------
+ * TrajDecoder/train_traj.py:179 (`net(x_cond, cond[...])` with net.train()) and :200 (`loss.backward()`: torch autograd over
+ * traj_model.py:170-200), fp32 throughout.  Rows are [clip][pos = dancer * seq + frame]; R = b * T token rows, Tp = T rounded up
+ * to 16, P = b * pairs music rows, L = n_layers.
+ *
+ * Dropout (traj_model.py:40 attn_drop, :45 resid_drop, :59 mlp[3]; model/utils.py PositionalEncoding.dropout at :106) uses the
+ * counter hash of csrc/train_common.h keyed by (seed, site, flat index in the reference's tensor):
+ *   TC_SITE_NAV_POS                      pos_embed.dropout on (b, T, 64)
+ *   TC_SITE_NAV_BLOCK(i, 0)              block i attn_drop on the probabilities (b, 4, T, T)
+ *   TC_SITE_NAV_BLOCK(i, 1)              block i resid_drop on (b, T, 128)
+ *   TC_SITE_NAV_BLOCK(i, 2)              block i mlp[3] on (b, T, 128)
+ * The backward regenerates every mask; no mask and no probability is stored.
+ * Limits: fp32; T <= 500; the element index is a 32-bit word that wraps, as csrc/train_common.h defines (the oracle wraps alike):
+ * attn_drop's b * 4 * T * T stays below 2^32 up to b = 4294 clips at T = 500, beyond which distinct elements share mask bits. */
+#define TC_SITE_NAV_POS 256
+#define TC_SITE_NAV_BLOCK(i, k) (260 + 4 * (i) + (k))
+
+/* float offsets of the gradients inside `grads`: the transformer blocks and the Decoder as tcdiff_nav_args packs them (the
+ * Decoder's last linear in the first 2 of 16 rows), then music_projection + cond_emb UNPADDED (W1 [438][876], b1, W2 [438][438],
+ * b2, W3 [64][438], b3, Wc [64][64], bc), then per LSTM layer W_ih [256][in], W_hh [256][64], b_ih, b_hh (in = 2, 64, 64). */
+#define TC_NAV_G_DEC(L) ((long)(L) * 198272)
+#define TC_NAV_G_MUSIC(L) (TC_NAV_G_DEC(L) + 50512)
+#define TC_NAV_G_MUSIC_SIZE (438 * 876 + 438 + 438 * 438 + 438 + 64 * 438 + 64 + 64 * 64 + 64)
+#define TC_NAV_G_LSTM(L) (TC_NAV_G_MUSIC(L) + TC_NAV_G_MUSIC_SIZE)
+#define TC_NAV_G_LSTM_SIZE (256 * (2 + 64 + 2) + 2 * 256 * (64 + 64 + 2))
+#define TC_NAV_G_SIZE(L) (TC_NAV_G_LSTM(L) + TC_NAV_G_LSTM_SIZE)
+#define TC_NAV_WG_CHUNKS 32 /* most row chunks of a weight gradient's first stage */
+#define TC_NAV_WG_PARTIAL (448 * 896 + 448) /* floats per chunk: the largest [N to 16][K to 64] weight tile plus its bias */
+
+typedef struct {
+    unsigned seed0, seed1;  /* the two seed words of this step's masks */
+    unsigned drop_thr;      /* floor(p * 2^32); 0 = every site an identity */
+    float drop_scale;       /* 1 / (1 - p) */
+    const float* cond;      /* [b][2 pairs][438]: the music frames the forward read (an odd last frame already dropped) */
+    const float* x_in;      /* [R][2]: the conditioning window (tcdiff_nav_args.traj is overwritten by the prediction) */
+    /* written by the forward, read by the backward */
+    float* lstm_gates;      /* [3][R][256] the activated gates i, f, g, o */
+    float* lstm_c;          /* [3][R][64] cell states */
+    float* lstm_h;          /* [3][R][64] hidden states */
+    float* xs;              /* [L + 1][R][128] every block's input rows and the last block's output */
+    float* xmid;            /* [L][R][128] the rows after the attention residual */
+    float* att_o;           /* [L][R][128] the attention's output before proj */
+    float* lse;             /* [L][b][4][Tp] log-sum-exp of every score row */
+    float* hid;             /* [L][R][512] the MLP's hidden rows before the GELU */
+    float* dec_z;           /* [R][320] the Decoder's pre-activations: 128 | 128 | 64 */
+    float* mus_z;           /* [P][896] music_projection's pre-activations: 448 | 448 */
+    /* tcdiff_nav_args.q / k / vt hold L images instead of 2 */
+    /* backward workspaces */
+    const float* d_out;     /* [R][2] the loss gradient of the prediction */
+    float* gx;              /* [R][128] gradient of the residual stream */
+    float* g_dec;           /* [R][336]: d z1 128 | d z2 128 | d z3 64 | d out 16 */
+    float* g_mpb;           /* [R][64] gradient of the Decoder's music columns, per token row */
+    float* g_m;             /* [R][128] gradient of mlp[2]'s output */
+    float* g_hid;           /* [R][512] gradient of mlp[0]'s output */
+    float* g_a;             /* [R][128] gradient of proj's output */
+    float* g_o;             /* [b][Tp][128] gradient of the attention's output (pad rows stay zero) */
+    float* delta;           /* [b][4][Tp] dO . O per row and head */
+    float* g_qkv;           /* [R][384] gradients of Q | K | V */
+    float* n1;              /* [R][128] LN1's output and */
+    float* n2;              /* [R][128] LN2's output of the block in hand: the LayerNorm statistics are deliberately NOT saved by
+                               the forward; the backward has the input rows in LDS, recomputes mean / rstd with the forward's
+                               expression and writes the normalised rows here for the weight-gradient products */
+    float* ln_part;         /* [b * ceil(T / 16)][4][128] per-workgroup sums for the LayerNorm weights */
+    float* g_me;            /* [P][64] gradient of cond_emb's output (rows past seq zero) */
+    float* g_mp;            /* [P][64] gradient of music_projection's output */
+    float* g_mz;            /* [P][896] gradients of music_projection's pre-activations */
+    float* g_gates;         /* [3][R][256] gradients of the LSTM's gate pre-activations */
+    float* partial;         /* [TC_NAV_WG_CHUNKS][TC_NAV_WG_PARTIAL] first stage of the weight-gradient reductions */
+    float* grads;           /* [TC_NAV_G_SIZE(L)] out: every parameter's gradient, assigned */
+} tcdiff_nav_train_args;
+
+/* The train-mode forward: tcdiff_nav_music_front + one window of tcdiff_nav_rollout (me_off = 0, mp_off = pairs - seq, no roll,
+ * no taps) with the four dropout sites live and the tensors above written out.  With drop_thr = 0 the prediction equals the
+ * inference path's bit for bit.  Replaces train_traj.py:179. */
+int tcdiff_nav_train_fwd(const tcdiff_nav_args* a, const tcdiff_nav_train_args* t, const float* wm, hipStream_t stream);
+
+/* The reverse pass of that forward, replacing train_traj.py:200 below `pre_traj`: Decoder, the blocks last to first (MLP and proj
+ * adjoints with LayerNorm / GELU / residual / dropout fused around the input-gradient products; attention backward flash-style
+ * from Q, K, V and the saved log-sum-exp with the mask regenerated; Q / K / V adjoint through LN1), the front (cond_emb half
+ * summed over dancers, both music row ranges added where they overlap, music_projection), the LSTM backward through time over
+ * the clip axis (the forward's wavefront reversed), and every weight / bias gradient as a fixed-order two-stage reduction: no
+ * floating-point atomics, the same bits from the same seed.  Inputs get no gradient. */
+int tcdiff_nav_train_bwd(const tcdiff_nav_args* a, const tcdiff_nav_train_args* t, const float* wm, hipStream_t stream);
+
 /* library identification */
 const char* tcdiff_version(void);
 

@@ -104,6 +104,14 @@ class NavArgs(C.Structure):
                 ("tap_blocks", _vp)]
 
 
+class NavTrainArgs(C.Structure):
+    """tcdiff_nav_train_args (include/tcdiff_hip.h): what the Navigator's train-mode forward saves and its backward works in."""
+    _fields_ = [("seed0", C.c_uint32), ("seed1", C.c_uint32), ("drop_thr", C.c_uint32), ("drop_scale", _f), ("cond", _vp), ("x_in", _vp)] + \
+        [(n, _vp) for n in ("lstm_gates", "lstm_c", "lstm_h", "xs", "xmid", "att_o", "lse", "hid", "dec_z", "mus_z", "d_out", "gx",
+                            "g_dec", "g_mpb", "g_m", "g_hid", "g_a", "g_o", "delta", "g_qkv", "n1", "n2", "ln_part", "g_me", "g_mp",
+                            "g_mz", "g_gates", "partial", "grads")]
+
+
 class AdanScalars(C.Structure):
     _fields_ = [(n, _f) for n in ("b1", "omb1", "b2", "omb2", "b3", "omb3", "cm", "cv", "cn", "eps", "lr", "denom")] + \
         [("first", _i)]
@@ -169,6 +177,9 @@ _SIGS = {
     # Dance-Beat Navigator (csrc/navigator.hip)
     "tcdiff_nav_music_front": [_vp, _i, _i, _vp, _vp, _vp, _vp],
     "tcdiff_nav_rollout": [C.POINTER(NavArgs), _i, _vp],
+    # training the Navigator (csrc/navigator.hip, csrc/navigator_train.hip)
+    "tcdiff_nav_train_fwd": [C.POINTER(NavArgs), C.POINTER(NavTrainArgs), _vp, _vp],
+    "tcdiff_nav_train_bwd": [C.POINTER(NavArgs), C.POINTER(NavTrainArgs), _vp, _vp],
 }
 
 EXPORTS = sorted(list(_SIGS) + ["tcdiff_version"])

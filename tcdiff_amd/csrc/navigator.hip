@@ -19,92 +19,20 @@
 // Lane l (r = l & 15, g = l >> 4) fetches k = k0 + 4 g .. 4 g + 3 of row r (A) / column r (W) and MFMA j of the four pairs element j
 // of both: the K order inside a dot product is permuted the same way for A and W, which only changes the fp32 summation order.  An
 // output row depends on its own input row only, never on which rows share the block or the launch.
-#include "common.h"
-#include "tcdiff_hip.h"
+#include "nav_common.h"
+#include "train_common.h"
 
 namespace {
-
-constexpr int NV_W = 128;        // transformer width
-constexpr int NV_LD = NV_W + 4;  // LDS row stride of a 128-wide block: rows shift by four banks
-constexpr int NV_R = 16;         // token rows per workgroup
-constexpr int NV_HID = 512;
-constexpr int NV_LSTM_S = 2;     // sequences per LSTM workgroup
-
-// packed per-block parameters (floats): tcdiff_amd/navigator.py writes this order
-constexpr int BK_LN1G = 0, BK_LN1B = 128, BK_WQ = 256, BK_BQ = BK_WQ + 16384, BK_WK = BK_BQ + 128, BK_BK = BK_WK + 16384,
-              BK_WV = BK_BK + 128, BK_BV = BK_WV + 16384, BK_WP = BK_BV + 128, BK_BP = BK_WP + 16384, BK_LN2G = BK_BP + 128,
-              BK_LN2B = BK_LN2G + 128, BK_W1 = BK_LN2B + 128, BK_B1 = BK_W1 + 65536, BK_W2 = BK_B1 + 512, BK_B2 = BK_W2 + 65536,
-              BK_SIZE = BK_B2 + 128;
-// packed Decoder: 192 -> 128 -> 128 -> 64 -> 2 (the last weight padded to 16 rows)
-constexpr int DC_W1 = 0, DC_B1 = DC_W1 + 128 * 192, DC_W2 = DC_B1 + 128, DC_B2 = DC_W2 + 16384, DC_W3 = DC_B2 + 128,
-              DC_B3 = DC_W3 + 64 * 128, DC_W4 = DC_B3 + 64, DC_B4 = DC_W4 + 16 * 64, DC_SIZE = DC_B4 + 16;
-// packed music front: 876 (880) -> 438 (448) -> 438 (448) -> 64, then cond_emb 64 -> 64
-constexpr int MU_K0 = 880, MU_N = 448;
-constexpr int MU_W1 = 0, MU_B1 = MU_W1 + MU_N * MU_K0, MU_W2 = MU_B1 + MU_N, MU_B2 = MU_W2 + MU_N * MU_N, MU_W3 = MU_B2 + MU_N,
-              MU_B3 = MU_W3 + 64 * MU_N, MU_WC = MU_B3 + 64, MU_BC = MU_WC + 64 * 64, MU_SIZE = MU_BC + 64;
-static_assert(BK_SIZE == 198272 && DC_SIZE == 50512 && MU_SIZE == 628736, "tcdiff_amd/navigator.py packs these sizes");
-
-DEVINL float leaky(float v) { return v > 0.f ? v : 0.01f * v; }
-DEVINL float gelu_erf(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752f)); }
-DEVINL float sigmoidf(float v) { return 1.f / (1.f + expf(-v)); }
-
-// out(row, col, value) for the 16 x (16 ntiles) product of As[16][lda] (LDS) and W[16 ntiles][ldw] (global); K % 16 == 0.
-// Wave wv of nw owns pairs of column tiles (two independent accumulator chains).
-template <class Epi>
-DEVINL void nav_mm16(const float* As, int lda, const float* __restrict__ W, int ldw, int ntiles, int K, int wv, int nw, Epi epi) {
-    const int lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
-    const float* a = As + r * lda + 4 * g;
-    for (int p = wv; 2 * p < ntiles; p += nw) {
-        const int t0 = 2 * p;
-        const bool two = t0 + 1 < ntiles;
-        const float* w0 = W + (long)(t0 * 16 + r) * ldw + 4 * g;
-        const float* w1 = two ? w0 + (long)16 * ldw : w0;
-        f32x4_t c0 = {0.f, 0.f, 0.f, 0.f}, c1 = c0;
-#pragma unroll 4
-        for (int k = 0; k < K; k += 16) {
-            const f32x4_t av = *reinterpret_cast<const f32x4_t*>(a + k);
-            const f32x4_t b0 = *reinterpret_cast<const f32x4_t*>(w0 + k);
-            const f32x4_t b1 = *reinterpret_cast<const f32x4_t*>(w1 + k);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], b0[j], c0, 0, 0, 0);
-                c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], b1[j], c1, 0, 0, 0);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            epi(4 * g + i, t0 * 16 + r, c0[i]);
-            if (two) epi(4 * g + i, t0 * 16 + 16 + r, c1[i]);
-        }
-    }
-}
-
-// nn.LayerNorm(128) of the 16 rows of Xs into Ns (biased variance, eps 1e-5): a wave takes four rows, a lane two columns
-DEVINL void nav_ln16(const float* Xs, float* Ns, const float* __restrict__ gam, const float* __restrict__ bet) {
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (int r = wv * 4; r < wv * 4 + 4; ++r) {
-        const float x0 = Xs[r * NV_LD + lane], x1 = Xs[r * NV_LD + 64 + lane];
-        float s = x0 + x1;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-        const float mean = s * (1.f / NV_W);
-        const float d0 = x0 - mean, d1 = x1 - mean;
-        float q = d0 * d0 + d1 * d1;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
-        const float rstd = 1.f / sqrtf(q * (1.f / NV_W) + 1e-5f);
-        Ns[r * NV_LD + lane] = d0 * rstd * gam[lane] + bet[lane];
-        Ns[r * NV_LD + 64 + lane] = d1 * rstd * gam[64 + lane] + bet[64 + lane];
-    }
-}
 
 // ---- LSTM over the clip axis ---------------------------------------------------------------------------------------------------
 // x [b][T][2]; wpk [3][128][256] (k < 64: weight_ih column k, zero beyond the layer's input width; k >= 64: weight_hh column k - 64;
 // 256 gate rows in PyTorch's order i, f, g, o); bih / bhh [3][256]; pe [>= T][64]; out [b][T][64] = h + pe; raw (or NULL) = h.
+// TR (the train-mode forward): pos_embed's dropout on h + pe, and every layer's activated gates, cell and hidden state written out.
+template <bool TR>
 __global__ __launch_bounds__(768) void nav_lstm_kernel(const float* __restrict__ x, const float* __restrict__ wpk,
                                                        const float* __restrict__ bih, const float* __restrict__ bhh,
                                                        const float* __restrict__ pe, float* __restrict__ out,
-                                                       float* __restrict__ raw, int b, int T) {
+                                                       float* __restrict__ raw, int b, int T, tcdiff_nav_train_args tr) {
     __shared__ __attribute__((aligned(16))) float hbuf[3][NV_LSTM_S][64];
     __shared__ float gates[3][NV_LSTM_S][256];
     const int l = threadIdx.x >> 8, j = threadIdx.x & 255;
@@ -171,9 +99,23 @@ __global__ __launch_bounds__(768) void nav_lstm_kernel(const float* __restrict__
             c = gf * c + gi * gg;
             const float h = go * tanhf(c);
             hbuf[l][s][u] = h;
+            if constexpr (TR) {
+                if (pos0 + s < T) {
+                    const long row = ((long)l * b + t) * T + pos0 + s;
+                    float* gs = tr.lstm_gates + row * 256 + u;
+                    gs[0] = gi, gs[64] = gf, gs[128] = gg, gs[192] = go;
+                    tr.lstm_c[row * 64 + u] = c;
+                    tr.lstm_h[row * 64 + u] = h;
+                }
+            }
             if (l == 2 && pos0 + s < T) {
                 const long o = ((long)t * T + pos0 + s) * 64 + u;
-                out[o] = h + pe[(pos0 + s) * 64 + u];
+                if constexpr (TR) {
+                    const DropCtx dc = drop_ctx_words(tr.seed0, tr.seed1, TC_SITE_NAV_POS, tr.drop_thr, tr.drop_scale);
+                    out[o] = drop_apply(dc, (uint32_t)o, h + pe[(pos0 + s) * 64 + u]);
+                } else {
+                    out[o] = h + pe[(pos0 + s) * 64 + u];
+                }
                 if (raw) raw[o] = h;
             }
         }
@@ -183,9 +125,10 @@ __global__ __launch_bounds__(768) void nav_lstm_kernel(const float* __restrict__
 
 // ---- music front: every frame pair of the song, once per rollout -----------------------------------------------------------------
 // cond [b][n][438]; row m = clip * pairs + p reads frames 2 p, 2 p + 1 (876 consecutive floats)
+// zs (the train-mode forward, else NULL): [rows][896] receives the two hidden layers' pre-activations
 __global__ __launch_bounds__(256) void nav_music_kernel(const float* __restrict__ cond, int n_frames, int pairs, int rows,
                                                         const float* __restrict__ wm, float* __restrict__ mp,
-                                                        float* __restrict__ me) {
+                                                        float* __restrict__ me, float* __restrict__ zs) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int LA = MU_K0 + 4, LH = MU_N + 4, LO = 68;
     float* As = smem;
@@ -204,10 +147,18 @@ __global__ __launch_bounds__(256) void nav_music_kernel(const float* __restrict_
     }
     __syncthreads();
     const float* b1 = wm + MU_B1;
-    nav_mm16(As, LA, wm + MU_W1, MU_K0, MU_N / 16, MU_K0, wv, 4, [&](int r, int c, float v) { H1[r * LH + c] = leaky(v + b1[c]); });
+    nav_mm16(As, LA, wm + MU_W1, MU_K0, MU_N / 16, MU_K0, wv, 4, [&](int r, int c, float v) {
+        const float z = v + b1[c];
+        if (zs && row0 + r < rows) zs[(long)(row0 + r) * (2 * MU_N) + c] = z;
+        H1[r * LH + c] = leaky(z);
+    });
     __syncthreads();
     const float* b2 = wm + MU_B2;
-    nav_mm16(H1, LH, wm + MU_W2, MU_N, MU_N / 16, MU_N, wv, 4, [&](int r, int c, float v) { H2[r * LH + c] = leaky(v + b2[c]); });
+    nav_mm16(H1, LH, wm + MU_W2, MU_N, MU_N / 16, MU_N, wv, 4, [&](int r, int c, float v) {
+        const float z = v + b2[c];
+        if (zs && row0 + r < rows) zs[(long)(row0 + r) * (2 * MU_N) + MU_N + c] = z;
+        H2[r * LH + c] = leaky(z);
+    });
     __syncthreads();
     const float* b3 = wm + MU_B3;
     nav_mm16(H2, LH, wm + MU_W3, MU_N, 4, MU_N, wv, 4, [&](int r, int c, float v) {
@@ -223,7 +174,10 @@ __global__ __launch_bounds__(256) void nav_music_kernel(const float* __restrict_
 }
 
 // ---- one transformer block of 16 rows --------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void nav_block_kernel(tcdiff_nav_args a, int layer, int win) {
+// TR (the train-mode forward): the three dropout sites of a block, Q / K / V and the residual stream kept per layer instead of
+// ping-pong / in place, and what the backward reads written out (tcdiff_nav_train_args).
+template <bool TR>
+__global__ __launch_bounds__(256) void nav_block_kernel(tcdiff_nav_args a, int layer, int win, tcdiff_nav_train_args tr) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Xs = smem;
     float* Ns = Xs + NV_R * NV_LD;
@@ -234,7 +188,9 @@ __global__ __launch_bounds__(256) void nav_block_kernel(tcdiff_nav_args a, int l
     const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
     const long set = (long)a.b * Tp * NV_W;                  // one ping-pong image of Q, K or V^T
     const int moff = win * a.win_stride;
-    float* xg = a.x + (long)clip * T * NV_W;
+    const long img = (long)a.b * T * NV_W;                   // TR: one layer's rows
+    float* xg = TR ? tr.xs + (layer + 1) * img + (long)clip * T * NV_W : a.x + (long)clip * T * NV_W;
+    const float* xin = TR ? xg - img : xg;
 
     if (layer < 0) {
         // [cond_emb(music rows of the conditioning side) repeated per dancer | LSTM output + positional encoding]
@@ -251,11 +207,11 @@ __global__ __launch_bounds__(256) void nav_block_kernel(tcdiff_nav_args a, int l
         __syncthreads();
     } else {
         const float* P = a.blocks + (long)layer * BK_SIZE;
-        const long cur = (long)(layer & 1) * set;
+        const long cur = (long)(TR ? layer : layer & 1) * set;
         const float* qg = a.q + cur + (long)clip * Tp * NV_W;
         for (int i = tid; i < NV_R * NV_W; i += 256) {
             const int r = i >> 7, c = i & 127, pos = row0 + r;
-            Xs[r * NV_LD + c] = pos < T ? xg[(long)pos * NV_W + c] : 0.f;
+            Xs[r * NV_LD + c] = pos < T ? xin[(long)pos * NV_W + c] : 0.f;
             Ns[r * NV_LD + c] = pos < T ? qg[(long)pos * NV_W + c] : 0.f;
         }
         __syncthreads();
@@ -283,6 +239,13 @@ __global__ __launch_bounds__(256) void nav_block_kernel(tcdiff_nav_args a, int l
                 }
                 s += __shfl_xor(s, 1);
                 s += __shfl_xor(s, 2);
+                if constexpr (TR) {
+                    const int pos = row0 + (lane >> 2);
+                    if (sub == 0 && pos < T) tr.lse[(((long)layer * a.b + clip) * 4 + wv) * Tp + pos] = m + logf(s);
+                    const DropCtx dc = drop_ctx_words(tr.seed0, tr.seed1, TC_SITE_NAV_BLOCK(layer, 0), tr.drop_thr, tr.drop_scale);
+                    const uint32_t base = (uint32_t)((((long)clip * 4 + wv) * T + pos) * T);
+                    for (int c = sub; c < T; c += 4) srow[c] = drop_apply(dc, base + (uint32_t)c, srow[c] / s);
+                } else
                 for (int c = sub; c < T; c += 4) srow[c] = srow[c] / s;
                 for (int c = T + sub; c < Tp; c += 4) srow[c] = 0.f;
             }
@@ -291,17 +254,44 @@ __global__ __launch_bounds__(256) void nav_block_kernel(tcdiff_nav_args a, int l
             __syncthreads();
         }
         const float* bp = P + BK_BP;
-        nav_mm16(Ys, NV_LD, P + BK_WP, NV_W, 8, NV_W, wv, 4, [&](int r, int c, float v) { Xs[r * NV_LD + c] += v + bp[c]; });
+        if constexpr (TR) {
+            float* og = tr.att_o + layer * img + (long)clip * T * NV_W;
+            for (int i = tid; i < NV_R * NV_W; i += 256)
+                if (row0 + (i >> 7) < T) og[(long)(row0 + (i >> 7)) * NV_W + (i & 127)] = Ys[(i >> 7) * NV_LD + (i & 127)];
+            const DropCtx dc = drop_ctx_words(tr.seed0, tr.seed1, TC_SITE_NAV_BLOCK(layer, 1), tr.drop_thr, tr.drop_scale);
+            nav_mm16(Ys, NV_LD, P + BK_WP, NV_W, 8, NV_W, wv, 4, [&](int r, int c, float v) {
+                Xs[r * NV_LD + c] += drop_apply(dc, (uint32_t)(((long)clip * T + row0 + r) * NV_W + c), v + bp[c]);
+            });
+        } else {
+            nav_mm16(Ys, NV_LD, P + BK_WP, NV_W, 8, NV_W, wv, 4, [&](int r, int c, float v) { Xs[r * NV_LD + c] += v + bp[c]; });
+        }
         __syncthreads();
+        if constexpr (TR) {
+            float* mg = tr.xmid + layer * img + (long)clip * T * NV_W;
+            for (int i = tid; i < NV_R * NV_W; i += 256)
+                if (row0 + (i >> 7) < T) mg[(long)(row0 + (i >> 7)) * NV_W + (i & 127)] = Xs[(i >> 7) * NV_LD + (i & 127)];
+        }
         nav_ln16(Xs, Ns, P + BK_LN2G, P + BK_LN2B);
         __syncthreads();
         constexpr int LH = NV_HID + 4;
         const float* b1 = P + BK_B1;
         nav_mm16(Ns, NV_LD, P + BK_W1, NV_W, NV_HID / 16, NV_W, wv, 4,
-                 [&](int r, int c, float v) { Big[r * LH + c] = gelu_erf(v + b1[c]); });
+                 [&](int r, int c, float v) {
+                     const float z = v + b1[c];
+                     if constexpr (TR)
+                         if (row0 + r < T) tr.hid[(((long)layer * a.b + clip) * T + row0 + r) * NV_HID + c] = z;
+                     Big[r * LH + c] = gelu_erf(z);
+                 });
         __syncthreads();
         const float* b2 = P + BK_B2;
-        nav_mm16(Big, LH, P + BK_W2, NV_HID, 8, NV_HID, wv, 4, [&](int r, int c, float v) { Xs[r * NV_LD + c] += v + b2[c]; });
+        if constexpr (TR) {
+            const DropCtx dc = drop_ctx_words(tr.seed0, tr.seed1, TC_SITE_NAV_BLOCK(layer, 2), tr.drop_thr, tr.drop_scale);
+            nav_mm16(Big, LH, P + BK_W2, NV_HID, 8, NV_HID, wv, 4, [&](int r, int c, float v) {
+                Xs[r * NV_LD + c] += drop_apply(dc, (uint32_t)(((long)clip * T + row0 + r) * NV_W + c), v + b2[c]);
+            });
+        } else {
+            nav_mm16(Big, LH, P + BK_W2, NV_HID, 8, NV_HID, wv, 4, [&](int r, int c, float v) { Xs[r * NV_LD + c] += v + b2[c]; });
+        }
         __syncthreads();
         float* tap = a.tap_blocks ? a.tap_blocks + ((long)layer * a.b + clip) * T * NV_W : nullptr;
         for (int i = tid; i < NV_R * NV_W; i += 256) {
@@ -317,7 +307,7 @@ __global__ __launch_bounds__(256) void nav_block_kernel(tcdiff_nav_args a, int l
     if (layer + 1 < a.n_layers) {
         // the next block's LN1 and Q / K / V: Q [clip][Tp][128], K [clip][head][Tp][32], V^T [clip][head][32][Tp]
         const float* P = a.blocks + (long)(layer + 1) * BK_SIZE;
-        const long nxt = (long)((layer + 1) & 1) * set;
+        const long nxt = (long)(TR ? layer + 1 : (layer + 1) & 1) * set;
         nav_ln16(Xs, Ns, P + BK_LN1G, P + BK_LN1B);
         __syncthreads();
         float* qo = a.q + nxt + (long)clip * Tp * NV_W;
@@ -346,11 +336,26 @@ __global__ __launch_bounds__(256) void nav_block_kernel(tcdiff_nav_args a, int l
         }
         __syncthreads();
         const float *d1 = D + DC_B1, *d2 = D + DC_B2, *d3 = D + DC_B3, *d4 = D + DC_B4;
-        nav_mm16(Big, LD, D + DC_W1, 192, 8, 192, wv, 4, [&](int r, int c, float v) { Ns[r * NV_LD + c] = leaky(v + d1[c]); });
+        nav_mm16(Big, LD, D + DC_W1, 192, 8, 192, wv, 4, [&](int r, int c, float v) {
+            const float z = v + d1[c];
+            if constexpr (TR)
+                if (row0 + r < T) tr.dec_z[((long)clip * T + row0 + r) * 320 + c] = z;
+            Ns[r * NV_LD + c] = leaky(z);
+        });
         __syncthreads();
-        nav_mm16(Ns, NV_LD, D + DC_W2, NV_W, 8, NV_W, wv, 4, [&](int r, int c, float v) { Ys[r * NV_LD + c] = leaky(v + d2[c]); });
+        nav_mm16(Ns, NV_LD, D + DC_W2, NV_W, 8, NV_W, wv, 4, [&](int r, int c, float v) {
+            const float z = v + d2[c];
+            if constexpr (TR)
+                if (row0 + r < T) tr.dec_z[((long)clip * T + row0 + r) * 320 + 128 + c] = z;
+            Ys[r * NV_LD + c] = leaky(z);
+        });
         __syncthreads();
-        nav_mm16(Ys, NV_LD, D + DC_W3, NV_W, 4, NV_W, wv, 4, [&](int r, int c, float v) { Ns[r * NV_LD + c] = leaky(v + d3[c]); });
+        nav_mm16(Ys, NV_LD, D + DC_W3, NV_W, 4, NV_W, wv, 4, [&](int r, int c, float v) {
+            const float z = v + d3[c];
+            if constexpr (TR)
+                if (row0 + r < T) tr.dec_z[((long)clip * T + row0 + r) * 320 + 256 + c] = z;
+            Ns[r * NV_LD + c] = leaky(z);
+        });
         __syncthreads();
         nav_mm16(Ns, NV_LD, D + DC_W4, 64, 1, 64, wv, 4, [&](int r, int c, float v) {
             const int pos = row0 + r;
@@ -367,10 +372,7 @@ __global__ __launch_bounds__(256) void nav_block_kernel(tcdiff_nav_args a, int l
 
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-}  // namespace
-
-extern "C" int tcdiff_nav_music_front(const float* cond, int b, int n_frames, const float* wm, float* mp, float* me,
-                                      hipStream_t stream) {
+int music_front(const float* cond, int b, int n_frames, const float* wm, float* mp, float* me, float* zs, hipStream_t stream) {
     if (!cond || !wm || !mp || !me || b < 1 || n_frames < 2) return TCDIFF_ERR_ARG;
     if (!al16(wm) || !al16(mp) || !al16(me)) return TCDIFF_ERR_ALIGN;
     const int pairs = n_frames / 2;
@@ -387,11 +389,21 @@ extern "C" int tcdiff_nav_music_front(const float* cond, int b, int n_frames, co
         ready = true;
     }
     nav_music_kernel<<<dim3((unsigned)((rows + NV_R - 1) / NV_R)), dim3(256), smem, stream>>>(cond, n_frames, pairs, (int)rows, wm,
-                                                                                              mp, me);
+                                                                                              mp, me, zs);
     return hipGetLastError() == hipSuccess ? TCDIFF_OK : TCDIFF_ERR_LAUNCH;
 }
 
-extern "C" int tcdiff_nav_rollout(const tcdiff_nav_args* a, int n_windows, hipStream_t stream) {
+}  // namespace
+
+extern "C" int tcdiff_nav_music_front(const float* cond, int b, int n_frames, const float* wm, float* mp, float* me,
+                                      hipStream_t stream) {
+    return music_front(cond, b, n_frames, wm, mp, me, nullptr, stream);
+}
+
+namespace {
+
+template <bool TR>
+int nav_windows(const tcdiff_nav_args* a, const tcdiff_nav_train_args& tr, int n_windows, hipStream_t stream) {
     if (!a || n_windows < 1 || a->b < 1 || a->dn < 1 || a->seq < 1 || a->n_layers < 1 || a->pairs < 1) return TCDIFF_ERR_ARG;
     if (!a->lstm_w || !a->lstm_bih || !a->lstm_bhh || !a->pe || !a->blocks || !a->dec || !a->me || !a->mp || !a->traj ||
         !a->lstm_out || !a->x || !a->q || !a->k || !a->vt)
@@ -412,8 +424,8 @@ extern "C" int tcdiff_nav_rollout(const tcdiff_nav_args* a, int n_windows, hipSt
     const int smem = (3 * NV_R * NV_LD + big) * (int)sizeof(float);
     static int ready = 0;
     if (ready < smem) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(nav_block_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem) !=
-            hipSuccess) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(nav_block_kernel<TR>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                smem) != hipSuccess) {
             (void)hipGetLastError();
             return TCDIFF_ERR_UNSUPPORTED;
         }
@@ -423,10 +435,27 @@ extern "C" int tcdiff_nav_rollout(const tcdiff_nav_args* a, int n_windows, hipSt
     tcdiff_nav_args aw = *a;
     for (int w = 0; w < n_windows; ++w) {
         if (w == 1) aw.tap_blocks = nullptr;                 // the per-stage taps record the first window only
-        nav_lstm_kernel<<<dim3((unsigned)((T + NV_LSTM_S - 1) / NV_LSTM_S)), dim3(768), 0, stream>>>(
-            a->traj, a->lstm_w, a->lstm_bih, a->lstm_bhh, a->pe, a->lstm_out, w == 0 ? a->tap_lstm : nullptr, a->b, T);
-        for (int layer = -1; layer < a->n_layers; ++layer) nav_block_kernel<<<grid, dim3(256), smem, stream>>>(aw, layer, w);
+        nav_lstm_kernel<TR><<<dim3((unsigned)((T + NV_LSTM_S - 1) / NV_LSTM_S)), dim3(768), 0, stream>>>(
+            a->traj, a->lstm_w, a->lstm_bih, a->lstm_bhh, a->pe, a->lstm_out, w == 0 ? a->tap_lstm : nullptr, a->b, T, tr);
+        for (int layer = -1; layer < a->n_layers; ++layer) nav_block_kernel<TR><<<grid, dim3(256), smem, stream>>>(aw, layer, w, tr);
         if (hipGetLastError() != hipSuccess) return TCDIFF_ERR_LAUNCH;
     }
     return TCDIFF_OK;
+}
+
+}  // namespace
+
+extern "C" int tcdiff_nav_rollout(const tcdiff_nav_args* a, int n_windows, hipStream_t stream) {
+    return nav_windows<false>(a, tcdiff_nav_train_args{}, n_windows, stream);
+}
+
+extern "C" int tcdiff_nav_train_fwd(const tcdiff_nav_args* a, const tcdiff_nav_train_args* t, const float* wm, hipStream_t stream) {
+    if (!a || !t || !wm || a->roll || a->tap_lstm || a->tap_blocks || a->me_off != 0 || a->mp_off != a->pairs - a->seq)
+        return TCDIFF_ERR_ARG;
+    if (!t->cond || !t->lstm_gates || !t->lstm_c || !t->lstm_h || !t->xs || !t->xmid || !t->att_o || !t->lse || !t->hid ||
+        !t->dec_z || !t->mus_z)
+        return TCDIFF_ERR_ARG;
+    const int rc = music_front(t->cond, a->b, 2 * a->pairs, wm, const_cast<float*>(a->mp), const_cast<float*>(a->me), t->mus_z, stream);
+    if (rc != TCDIFF_OK) return rc;
+    return nav_windows<true>(a, *t, 1, stream);
 }

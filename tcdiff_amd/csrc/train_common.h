@@ -36,6 +36,14 @@ DEVINL DropCtx drop_ctx(const int* seed, int site, uint32_t thr, float scale) {
     d.scale = scale;
     return d;
 }
+// the same with the two seed words passed as kernel arguments
+DEVINL DropCtx drop_ctx_words(uint32_t s0, uint32_t s1, int site, uint32_t thr, float scale) {
+    DropCtx d;
+    d.key = tc_fmix32(s0 ^ (0x9E3779B9u * (uint32_t)(site + 1))) ^ s1;
+    d.thr = thr;
+    d.scale = scale;
+    return d;
+}
 DEVINL bool drop_keep(const DropCtx& d, uint32_t x) { return tc_fmix32((x * 0x9E3779B1u) ^ d.key) >= d.thr; }
 DEVINL float drop_apply(const DropCtx& d, uint32_t x, float v) { return drop_keep(d, x) ? v * d.scale : 0.0f; }
 

@@ -1,5 +1,6 @@
 """The Dance-Beat Navigator on the MI355X: `TrajDecoder` (TrajDecoder/model/traj_model.py:125-200) and the sliding-window
-rollout of `TCDiff.test_loop` (TCDiff.py:526-547), as HIP kernels (csrc/navigator.hip), inference only.
+rollout of `TCDiff.test_loop` (TCDiff.py:526-547), as HIP kernels (csrc/navigator.hip); `TrajTrainer` beside the module is the
+train-mode forward and the backward pass of TrajDecoder/train_traj.py (csrc/navigator_train.hip).
 
     traj_model = TrajDecoder(nfeats=2, trans_layer=6, window_size=100)
     traj_model.load_state_dict(ckpt["net"], strict=True)                 # the reference's checkpoint, key for key
@@ -116,7 +117,8 @@ class TrajDecoder(nn.Module):
 
     def train(self, mode: bool = True):
         if mode:
-            raise L.TcdiffError("TrajDecoder is inference only: training the Navigator (TrajDecoder/train_traj.py) is not built")
+            raise L.TcdiffError("TrajDecoder stays in eval mode: the training step of TrajDecoder/train_traj.py runs through "
+                                "navigator.TrajTrainer(net), not net.train()")
         return super().train(False)
 
     # ---- weights ------------------------------------------------------------------------------------------------------------------
@@ -187,10 +189,11 @@ class TrajDecoder(nn.Module):
 
     def _check(self, x, music):
         if self.training:
-            raise L.TcdiffError("TrajDecoder is inference only: training the Navigator (TrajDecoder/train_traj.py) is not built")
+            raise L.TcdiffError("TrajDecoder stays in eval mode: the training step of TrajDecoder/train_traj.py runs through "
+                                "navigator.TrajTrainer(net), not net.train()")
         if torch.is_grad_enabled() and (x.requires_grad or music.requires_grad):
-            raise L.TcdiffError("TrajDecoder: inputs that require grad need the Navigator's training step "
-                                "(TrajDecoder/train_traj.py), which is not built")
+            raise L.TcdiffError("TrajDecoder: inputs get no gradient (TrajDecoder/train_traj.py never asks for one); the parameters' "
+                                "gradients come from navigator.TrajTrainer(net)")
         dev = self.lstm.weight_ih_l0.device
         if dev.type != "cuda" or x.device != dev or music.device != dev:
             raise L.TcdiffError("TrajDecoder runs on MI355X only: move the module and its inputs to cuda (no CPU fallback)")
@@ -274,3 +277,186 @@ def rollout(model: TrajDecoder, x_traj_xy, cond, step: int = 25, taps=None):
     if taps is not None:
         model._fill_taps(taps, pl, b, pairs)
     return pl["roll"].clone()
+
+
+# ---- training (TrajDecoder/train_traj.py) ------------------------------------------------------------------------------------------
+SITE_POS = 256                      # TC_SITE_NAV_POS: pos_embed.dropout on (b, T, 64)
+
+
+def site_block(i: int, k: int) -> int:
+    """TC_SITE_NAV_BLOCK: block i, k = 0 attn_drop on (b, 4, T, T), 1 resid_drop on (b, T, 128), 2 mlp[3] on (b, T, 128)"""
+    return 260 + 4 * i + k
+
+
+_WG_CHUNKS, _WG_PARTIAL = 32, 448 * 896 + 448          # TC_NAV_WG_CHUNKS, TC_NAV_WG_PARTIAL
+_G_MUSIC = 438 * 876 + 438 + 438 * 438 + 438 + 64 * 438 + 64 + 64 * 64 + 64
+_G_LSTM = 256 * (2 + 64 + 2) + 2 * 256 * (64 + 64 + 2)
+
+
+class _TrajTrainFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, trainer, x, music, seed, *params):
+        ctx.trainer, ctx.n = trainer, len(params)
+        out = trainer._forward(x, music, seed)
+        ctx.gen = trainer._gen
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        ctx.trainer._backward(d_out, ctx.gen)
+        return (None,) * (4 + ctx.n)
+
+
+class TrajTrainer:
+    """The training step of TrajDecoder/train_traj.py:179-201 for a `TrajDecoder`, which itself stays in eval mode:
+
+        trainer = TrajTrainer(net, dropout=0.1)
+        pre_traj = trainer(x_cond, cond[:, m0:m1])          # train-mode forward, ONE autograd node
+        loss = ...; optimizer.zero_grad(); loss.backward(); optimizer.step()
+
+    `trainer(x, music, seed=None)` is traj_model.py:170-200 in train mode -- the four live dropout sites (pos_embed, and per
+    block attn_drop, resid_drop, mlp[3]) with counter-hash masks keyed by (seed, site, flat index of the reference's tensor); a
+    `seed` of None draws two words from torch's generator.  Its backward is the HIP reverse pass: it assigns `.grad` of every
+    parameter the forward uses (or adds to a `.grad` that is there); `trans_extractor.traj_emb.*` keep None and inputs get no
+    gradient.  fp32, the inference path's shape limits, one forward outstanding per trainer.
+
+    Allocation: workspaces are planned per shape and the seed travels as two kernel-argument words, so a step with the usual
+    `optimizer.zero_grad()` (set_to_none=True) allocates one tensor between its first and last launch -- the (b, dn, seq, 2)
+    prediction handed to autograd, which the caller owns.  With `zero_grad(set_to_none=False)`, or when gradients are accumulated
+    over several backwards, every `.grad` still is a view of the gradient buffer, which must not be overwritten: the backward then
+    takes a fresh buffer each time."""
+
+    def __init__(self, net: TrajDecoder, dropout: float = 0.1):
+        if not isinstance(net, TrajDecoder):
+            raise L.TcdiffError("TrajTrainer trains a tcdiff_amd.TrajDecoder")
+        if not 0.0 <= float(dropout) < 1.0:
+            raise L.TcdiffError(f"TrajTrainer: dropout must be in [0, 1), got {dropout}")
+        self.net, self.dropout = net, float(dropout)
+        self._plans, self._gen, self._pending, self._flat, self._views = {}, 0, None, None, None
+
+    # ---- the parameters that receive a gradient, with their place in the flat gradient buffer ----------------------------------
+    def _slots(self):
+        n, out, off = self.net, [], 0
+        for blk in n.trans_extractor.blocks:
+            a = blk.attn
+            for t in (blk.ln1.weight, blk.ln1.bias, a.query.weight, a.query.bias, a.key.weight, a.key.bias, a.value.weight,
+                      a.value.bias, a.proj.weight, a.proj.bias, blk.ln2.weight, blk.ln2.bias, blk.mlp[0].weight, blk.mlp[0].bias,
+                      blk.mlp[2].weight, blk.mlp[2].bias):
+                out.append((t, off))
+                off += t.numel()
+        assert off == n.trans_layer * _BK
+        d = n.Decoder
+        for t in (d[0].weight, d[0].bias, d[2].weight, d[2].bias, d[4].weight, d[4].bias):
+            out.append((t, off))
+            off += t.numel()
+        out += [(d[6].weight, off), (d[6].bias, off + 16 * 64)]             # the last linear sits in 2 of 16 padded rows
+        off = n.trans_layer * _BK + _DC
+        m, ce = n.music_projection, n.trans_extractor.cond_emb
+        for t in (m[0].weight, m[0].bias, m[2].weight, m[2].bias, m[4].weight, m[4].bias, ce.weight, ce.bias):
+            out.append((t, off))
+            off += t.numel()
+        assert off == n.trans_layer * _BK + _DC + _G_MUSIC
+        for l in range(3):
+            for nm in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"):
+                t = getattr(n.lstm, f"{nm}_l{l}")
+                out.append((t, off))
+                off += t.numel()
+        assert off == n.trans_layer * _BK + _DC + _G_MUSIC + _G_LSTM
+        return out, off
+
+    def _plan(self, dev, b, dn, seq, pairs):
+        key = (str(dev), b, dn, seq, pairs)
+        pl = self._plans.get(key)
+        if pl is None:
+            T, Ly = dn * seq, self.net.trans_layer
+            Tp, R, P = K.round_up(T, 16), b * dn * seq, b * pairs
+            z = lambda *s: torch.zeros(*s, device=dev, dtype=torch.float32)
+            pl = dict(cond=z(b, 2 * pairs, 438), x_in=z(R, 2), traj=z(b, T, 2),
+                      lstm_out=z(b, T, 64), x=z(16), q=z(Ly, b, Tp, 128), k=z(Ly, b, 4, Tp, 32), vt=z(Ly, b, 4, 32, Tp),
+                      mp=z(b, pairs, 64), me=z(b, pairs, 64), lstm_gates=z(3, R, 256), lstm_c=z(3, R, 64), lstm_h=z(3, R, 64),
+                      xs=z(Ly + 1, R, 128), xmid=z(Ly, R, 128), att_o=z(Ly, R, 128), lse=z(Ly, b, 4, Tp), hid=z(Ly, R, 512),
+                      dec_z=z(R, 320), mus_z=z(P, 896), d_out=z(R, 2), gx=z(R, 128), g_dec=z(R, 336), g_mpb=z(R, 64),
+                      g_m=z(R, 128), g_hid=z(R, 512), g_a=z(R, 128), g_o=z(b, Tp, 128), delta=z(b, 4, Tp), g_qkv=z(R, 384),
+                      n1=z(R, 128), n2=z(R, 128), ln_part=z(b * (Tp // 16), 4, 128), g_me=z(P, 64), g_mp=z(P, 64), g_mz=z(P, 896),
+                      g_gates=z(3, R, 256), partial=z(_WG_CHUNKS, _WG_PARTIAL))
+            if len(self._plans) >= 2:
+                self._plans.clear()
+            self._plans[key] = pl
+        return pl
+
+    def _args(self, pl, wt, b, dn, seq, pairs, seed):
+        a = L.NavArgs(b=b, dn=dn, seq=seq, n_layers=self.net.trans_layer, pairs=pairs, me_off=0, mp_off=pairs - seq, win_stride=0,
+                      step=0, roll_frames=0, roll_off=0, lstm_w=K._p(wt["lstm_w"]), lstm_bih=K._p(wt["bih"]),
+                      lstm_bhh=K._p(wt["bhh"]), pe=K._p(wt["pe"]), blocks=K._p(wt["blocks"]), dec=K._p(wt["dec"]),
+                      me=K._p(pl["me"]), mp=K._p(pl["mp"]), traj=K._p(pl["traj"]), lstm_out=K._p(pl["lstm_out"]), x=K._p(pl["x"]),
+                      q=K._p(pl["q"]), k=K._p(pl["k"]), vt=K._p(pl["vt"]), roll=None, tap_lstm=None, tap_blocks=None)
+        thr, scale = K.drop_params(self.dropout)
+        t = L.NavTrainArgs(seed0=seed[0] & 0xFFFFFFFF, seed1=seed[1] & 0xFFFFFFFF, drop_thr=thr, drop_scale=scale,
+                           grads=K._p(self._flat))
+        for name, _ in L.NavTrainArgs._fields_:
+            if name in pl:
+                setattr(t, name, K._p(pl[name]))
+        return a, t
+
+    def __call__(self, x, music_feat, seed=None):
+        net = self.net
+        dev = net._check(x, music_feat)
+        if x.requires_grad or music_feat.requires_grad:
+            raise L.TcdiffError("TrajTrainer: inputs get no gradient (TrajDecoder/train_traj.py never asks for one)")
+        if x.dtype != torch.float32 or music_feat.dtype != torch.float32:
+            raise L.TcdiffError("TrajTrainer: fp32 inputs only")
+        if x.shape[2] > music_feat.shape[1] // 2:
+            raise L.TcdiffError(f"TrajTrainer: {music_feat.shape[1]} music frames give {music_feat.shape[1] // 2} pairs, fewer than "
+                                f"seq = {x.shape[2]}")
+        if seed is None:
+            seed = tuple(int(v) for v in torch.randint(0, 2 ** 31 - 1, (2,)))
+        slots, _ = self._slots()
+        params = [p for p, _ in slots if p.requires_grad]
+        return _TrajTrainFn.apply(self, x, music_feat, (int(seed[0]), int(seed[1])), *params)
+
+    def _forward(self, x, music, seed):
+        net = self.net
+        dev = x.device
+        b, dn, seq, _ = x.shape
+        pairs = music.shape[1] // 2
+        wt = net._weights()
+        pl = self._plan(dev, b, dn, seq, pairs)
+        if self._flat is None or self._flat.device != dev:
+            self._new_flat(dev)
+        pl["cond"].copy_(music.detach()[:, :2 * pairs])
+        pl["x_in"].copy_(x.detach().reshape(b * dn * seq, 2))
+        pl["traj"].copy_(x.detach().reshape(b, dn * seq, 2))
+        a, t = self._args(pl, wt, b, dn, seq, pairs, seed)
+        L.check(L.load().tcdiff_nav_train_fwd(C.byref(a), C.byref(t), K._p(wt["music"]), K.stream()), "tcdiff_nav_train_fwd")
+        self._gen += 1
+        self._pending = dict(gen=self._gen, pl=pl, wt=wt, shape=(b, dn, seq, pairs), seed=seed)
+        return pl["traj"].reshape(b, dn, seq, 2).clone()
+
+    def _new_flat(self, dev):
+        slots, n = self._slots()
+        self._flat = torch.zeros(n, device=dev, dtype=torch.float32)
+        self._views = [(p, self._flat[off:off + p.numel()].view(p.shape)) for p, off in slots]
+
+    def _backward(self, d_out, gen):
+        pd = self._pending
+        if pd is None or pd["gen"] != gen:
+            raise L.TcdiffError("TrajTrainer: backward without its forward (one forward may be outstanding per trainer; run forward "
+                                "and backward in pairs)")
+        self._pending = None
+        pl, wt = pd["pl"], pd["wt"]
+        b, dn, seq, pairs = pd["shape"]
+        # a .grad that still is a view of the buffer (the caller accumulates instead of zero_grad): never overwrite it
+        base = self._flat.untyped_storage().data_ptr()
+        if any(p.grad is not None and p.grad.untyped_storage().data_ptr() == base for p, _ in self._views):
+            self._new_flat(self._flat.device)
+        pl["d_out"].copy_(d_out.reshape(b * dn * seq, 2))
+        a, t = self._args(pl, wt, b, dn, seq, pairs, pd["seed"])
+        L.check(L.load().tcdiff_nav_train_bwd(C.byref(a), C.byref(t), K._p(wt["music"]), K.stream()), "tcdiff_nav_train_bwd")
+        with torch.no_grad():
+            for p, v in self._views:
+                if not p.requires_grad:
+                    continue
+                if p.grad is None:
+                    p.grad = v
+                else:
+                    p.grad.add_(v)
