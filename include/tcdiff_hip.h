@@ -778,6 +778,25 @@ typedef struct {
  * TC_ERR_UNSUPPORTED for T > 500 (PositionalEncoding's max_len: the reference raises there too). */
 int tcdiff_nav_rollout(const tcdiff_nav_args* a, int n_windows, hipStream_t stream);
 
+/* The hand-off to the sampler (csrc/handoff.hip; TCDiff.py:543-556, TrajDecoder/train_traj.py:245-259): the forward Kalman
+ * filter of TrajDecoder/utils/utils_model.py:10-74 over every (clip, dancer) trajectory, the zero z channel and the frame-major
+ * token order, one launch, one thread per trajectory.
+ * traj: DEVICE fp32, element (clip, dancer, frame, channel) at traj[clip * s_b + dancer * s_dn + frame * s_f + channel * s_c]
+ *   (element strides: any view -- the rollout's buffer, x[:, :, :, [4, 5]] -- is read in place); b x dn x frames x 2.
+ * State (x, y, vx, vy) in float64, started at the first sample with zero velocity; per frame x = F x (constant velocity over
+ * dt), then residual = z - H x, x += K_t residual, every product and sum rounded on its own; the filtered position is rounded
+ * once to fp32.
+ * gains: DEVICE float64 [frames][4][2], K_t of P = F P F^T + Q, S = H P H^T + R, K = P H^T S^-1 and the Joseph-form update from
+ *   P0 = 10 I (data-independent: computed on the host once per (frames, dt, Q, R), tcdiff_amd/io.py kalman_gains).
+ * scale / min_: both NULL, or HOST float [3]: the outputs become (clamp(v, -1, 1) - min_[ch]) / scale_[ch] (Normalizer.unnormalize
+ *   of the zero-padded triple, dataset/preprocess.py:39-43; clamp keeps NaN), two rounded fp32 operations, z channel included.
+ * smoothed (optional): [b][dn][frames][2].  x0 (optional): [b][frames * dn][3], token frame * dn + dancer, channels (x, y, z) with
+ *   z = 0 or its un-normalised value, written by the kernel (the buffer need not be zeroed).  At least one of the two.
+ * TC_ERR_ARG for a NULL traj / gains, no output, b, dn or frames < 1, or only one of scale / min_; TC_ERR_UNSUPPORTED for more
+ * than 2^31 - 1 workgroups of 64 trajectories. */
+int tcdiff_nav_handoff(const float* traj, long s_b, long s_dn, long s_f, long s_c, int b, int dn, int frames, double dt,
+                       const double* gains, const float* scale, const float* min_, float* smoothed, float* x0, hipStream_t stream);
+
 /* ---- training the Navigator (csrc/navigator.hip train-mode forward, csrc/navigator_train.hip backward) ----------------------
  * TrajDecoder/train_traj.py:179 (`net(x_cond, cond[...])` with net.train()) and :200 (`loss.backward()`: torch autograd over
  * traj_model.py:170-200), fp32 throughout.  Rows are [clip][pos = dancer * seq + frame]; R = b * T token rows, Tp = T rounded up

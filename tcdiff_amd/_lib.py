@@ -177,6 +177,8 @@ _SIGS = {
     # Dance-Beat Navigator (csrc/navigator.hip)
     "tcdiff_nav_music_front": [_vp, _i, _i, _vp, _vp, _vp, _vp],
     "tcdiff_nav_rollout": [C.POINTER(NavArgs), _i, _vp],
+    # the hand-off to the sampler (csrc/handoff.hip)
+    "tcdiff_nav_handoff": [_vp, _l, _l, _l, _l, _i, _i, _i, C.c_double, _vp, C.POINTER(_f), C.POINTER(_f), _vp, _vp, _vp],
     # training the Navigator (csrc/navigator.hip, csrc/navigator_train.hip)
     "tcdiff_nav_train_fwd": [C.POINTER(NavArgs), C.POINTER(NavTrainArgs), _vp, _vp],
     "tcdiff_nav_train_bwd": [C.POINTER(NavArgs), C.POINTER(NavTrainArgs), _vp, _vp],

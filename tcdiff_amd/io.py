@@ -176,6 +176,30 @@ def x0_from_trajectory(traj_xy: torch.Tensor) -> torch.Tensor:
     return traj.permute(0, 2, 1, 3).reshape(bs, seq * dn, 3)
 
 
+def kalman_gains(frames: int, dt=1.0, process_noise_std=1e-2, measurement_noise_std=1e-1) -> np.ndarray:
+    """The gains K_t of `kalman_smooth_batch`'s filter, (frames, 4, 2) float64: P = F P F^T + Q, S = H P H^T + R,
+    K = P H^T S^-1, P = (I - K H) P (I - K H)^T + K R K^T (Joseph form) from P0 = 10 I, in filterpy's operation order.  The
+    covariance recursion does not depend on the data: the gains are a function of (frames, dt, process_noise_std,
+    measurement_noise_std) alone.  `kalman_smooth_batch` runs its state update against them on the host,
+    `navigator.smooth_x0` keeps them on the device for csrc/handoff.hip."""
+    F = np.array([[1, 0, dt, 0], [0, 1, 0, dt], [0, 0, 1, 0], [0, 0, 0, 1]], dtype=np.float64)
+    H = np.array([[1, 0, 0, 0], [0, 1, 0, 0]], dtype=np.float64)
+    R = np.eye(2) * measurement_noise_std ** 2
+    Q = np.eye(4) * process_noise_std
+    I4 = np.eye(4)
+    P = np.eye(4) * 10.0
+    gains = np.zeros((frames, 4, 2), dtype=np.float64)
+    for t in range(frames):
+        P = F @ P @ F.T + Q                           # predict
+        PHT = P @ H.T                                 # update
+        S = H @ PHT + R
+        K = PHT @ np.linalg.inv(S)
+        I_KH = I4 - K @ H
+        P = I_KH @ P @ I_KH.T + K @ R @ K.T
+        gains[t] = K
+    return gains
+
+
 def kalman_smooth_batch(xy_batch, dt=1.0, process_noise_std=1e-2, measurement_noise_std=1e-1):
     """Forward Kalman filter over every (clip, dancer) xy trajectory of `xy_batch` (batch, dancers, frames, 2) -> same shape
     and dtype: the smoothing step between the Dance-Beat Navigator's output and `x_0` (TCDiff.py:546; defined in
@@ -184,11 +208,11 @@ def kalman_smooth_batch(xy_batch, dt=1.0, process_noise_std=1e-2, measurement_no
     :49-53), R = measurement_noise_std^2 I; per frame one predict and one update, the filtered position is the output.
 
     The reference runs `filterpy.kalman.KalmanFilter` (filterpy==1.4.5, requirements.txt:69; NOT installed here and not
-    under /root/reference: **parity unpinned**), whose published predict / update are written out below in its operation
-    order: x = F x, P = F P F^T + Q; y = z - H x, S = H P H^T + R, K = P H^T S^-1, x += K y, P = (I - K H) P (I - K H)^T +
-    K R K^T (Joseph form), all in float64.  The covariance recursion does not depend on the data, so P and K are advanced once
-    per frame for ALL trajectories and only the state update is batched; a plain per-trajectory loop (tests/test_io_cpu.py)
-    gives the same numbers."""
+    under /root/reference: **parity unpinned**), whose published predict / update are written out here and in `kalman_gains`
+    in its operation order: x = F x, P = F P F^T + Q; y = z - H x, S = H P H^T + R, K = P H^T S^-1, x += K y, P = (I - K H) P
+    (I - K H)^T + K R K^T (Joseph form), all in float64.  The covariance recursion does not depend on the data, so P and K are
+    advanced once per frame for ALL trajectories (`kalman_gains`) and only the state update is batched; a plain per-trajectory
+    loop (tests/test_io_cpu.py, tests/handoff_ref.py) gives the same numbers."""
     xy = np.asarray(xy_batch)
     if xy.ndim != 4 or xy.shape[-1] != 2:
         raise ValueError(f"xy_batch must be (batch, dancers, frames, 2), got {xy.shape}")
@@ -198,23 +222,14 @@ def kalman_smooth_batch(xy_batch, dt=1.0, process_noise_std=1e-2, measurement_no
         return out
     F = np.array([[1, 0, dt, 0], [0, 1, 0, dt], [0, 0, 1, 0], [0, 0, 0, 1]], dtype=np.float64)
     H = np.array([[1, 0, 0, 0], [0, 1, 0, 0]], dtype=np.float64)
-    R = np.eye(2) * measurement_noise_std ** 2
-    Q = np.eye(4) * process_noise_std
-    I4 = np.eye(4)
-    P = np.eye(4) * 10.0
+    gains = kalman_gains(seq, dt, process_noise_std, measurement_noise_std)
     z = xy.reshape(bs * dn, seq, 2)
     x = np.zeros((bs * dn, 4), dtype=np.float64)
     x[:, :2] = z[:, 0]
     for t in range(seq):
         x = x @ F.T                                   # predict
-        P = F @ P @ F.T + Q
         y = z[:, t] - x @ H.T                         # update
-        PHT = P @ H.T
-        S = H @ PHT + R
-        K = PHT @ np.linalg.inv(S)
-        x = x + y @ K.T
-        I_KH = I4 - K @ H
-        P = I_KH @ P @ I_KH.T + K @ R @ K.T
+        x = x + y @ gains[t].T
         out.reshape(bs * dn, seq, 2)[:, t] = x[:, :2]
     return out
 

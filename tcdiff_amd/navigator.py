@@ -6,7 +6,8 @@ train-mode forward and the backward pass of TrajDecoder/train_traj.py (csrc/navi
     traj_model.load_state_dict(ckpt["net"], strict=True)                 # the reference's checkpoint, key for key
     traj_model.cuda().eval()
     x_traj = rollout(traj_model, x[:, :, :, [4, 5]], cond, step=25)      # (b, dn, window + n_windows * step, 2)
-    x_0 = tcdiff_amd.io.x0_from_navigator(x_traj)                        # Kalman smoothing, zero z, frame-major
+    x_0 = smooth_x0(x_traj)                                              # Kalman smoothing, zero z, frame-major (csrc/handoff.hip)
+    x_0 = rollout_x0(traj_model, x[:, :, :, [4, 5]], cond, step=25)      # both, nothing in between
 
 What the module computes, restated (everything fp32, eval-mode dropouts are identities):
 
@@ -34,6 +35,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
+from . import io as tio
 from . import kernels as K
 
 MAX_POS = 500                      # PositionalEncoding max_len (model/utils.py:12)
@@ -250,12 +252,8 @@ def window_starts(cond_len: int, window: int, step: int):
     return range(0, cond_len + 1 - (window + step) * 2, step * 2)
 
 
-def rollout(model: TrajDecoder, x_traj_xy, cond, step: int = 25, taps=None):
-    """TCDiff.py:526-547: `x_traj_xy` (b, dn, frames >= window, 2) gives the first window; every window of (window + step) * 2
-    music frames, moved by step * 2, predicts the next window from the previous one and contributes its last `step` frames.
-    Returns (b, dn, window + n_windows * step, 2) on the device; a `cond` too short for one window returns the initial window (the
-    reference's empty range).  The music front runs once for the whole `cond`; between the first and the last launch there is no
-    torch op, no allocation and no host synchronisation."""
+def _rollout_check(model, x_traj_xy, cond, step):
+    """`rollout`'s argument checks: the first window (a view), the device and the number of windows."""
     window = model.window_size
     if step < 1 or step > window:
         raise L.TcdiffError(f"rollout: step must be in 1 .. window_size = {window}, got {step}")
@@ -263,10 +261,14 @@ def rollout(model: TrajDecoder, x_traj_xy, cond, step: int = 25, taps=None):
         raise L.TcdiffError(f"rollout: x_traj_xy must be (b, dn, >= {window} frames, 2), got {tuple(x_traj_xy.shape)}")
     first = x_traj_xy[:, :, :window]
     dev = model._check(first, cond)
+    return first, dev, len(window_starts(cond.shape[1], window, step))
+
+
+def _rollout_launch(model, first, dev, cond, step, n_windows, taps):
+    """`rollout`'s launches for n_windows >= 1.  Returns the plan: its "roll" buffer holds the trajectories until the next rollout
+    of this shape.  Every torch op (the copies into the plan) comes before the first launch."""
+    window = model.window_size
     b, dn = first.shape[:2]
-    n_windows = len(window_starts(cond.shape[1], window, step))
-    if n_windows == 0:
-        return first.detach().to(torch.float32).clone()
     pairs = cond.shape[1] // 2
     wt = model._weights()
     pl = model._plan(dev, b, dn, window, pairs, window + n_windows * step, taps is not None)
@@ -274,9 +276,120 @@ def rollout(model: TrajDecoder, x_traj_xy, cond, step: int = 25, taps=None):
     pl["traj"].copy_(first.detach().reshape(b, dn * window, 2))
     pl["roll"][:, :, :window].copy_(first.detach())
     model._launch(pl, wt, condc, b, dn, window, pairs, n_windows, 0, step, step, step, window)
+    return pl
+
+
+def rollout(model: TrajDecoder, x_traj_xy, cond, step: int = 25, taps=None):
+    """TCDiff.py:526-547: `x_traj_xy` (b, dn, frames >= window, 2) gives the first window; every window of (window + step) * 2
+    music frames, moved by step * 2, predicts the next window from the previous one and contributes its last `step` frames.
+    Returns (b, dn, window + n_windows * step, 2) on the device; a `cond` too short for one window returns the initial window (the
+    reference's empty range).  The music front runs once for the whole `cond`; between the first and the last launch there is no
+    torch op, no allocation and no host synchronisation."""
+    first, dev, n_windows = _rollout_check(model, x_traj_xy, cond, step)
+    if n_windows == 0:
+        return first.detach().to(torch.float32).clone()
+    pl = _rollout_launch(model, first, dev, cond, step, n_windows, taps)
     if taps is not None:
-        model._fill_taps(taps, pl, b, pairs)
+        model._fill_taps(taps, pl, first.shape[0], cond.shape[1] // 2)
     return pl["roll"].clone()
+
+
+# ---- the hand-off to the sampler (TCDiff.py:543-556, TrajDecoder/train_traj.py:245-259) ---------------------------------------------
+_GAINS = {}                        # (device, frames, dt, q, r) -> the filter's gains K_t on the device, float64 (frames, 4, 2)
+
+
+def _gains(dev, frames, dt, q, r):
+    """io.kalman_gains on the device: computed on the host and copied once per key, read by every later launch."""
+    key = (str(dev), frames, float(dt), float(q), float(r))
+    g = _GAINS.get(key)
+    if g is None:
+        if len(_GAINS) >= 8:
+            del _GAINS[next(iter(_GAINS))]                 # the oldest key only: the other tables stay on the device
+        g = _GAINS[key] = torch.from_numpy(tio.kalman_gains(frames, *key[2:])).to(dev)
+    return g
+
+
+def _handoff_prepare(shape, dev, dt, q, r, normalizer, out, return_smoothed):
+    """Everything the hand-off launch needs besides its input -- the gains, the outputs, the normalizer's six numbers -- so that
+    `rollout_x0` can have it ready before the rollout's first launch."""
+    b, dn, frames, _ = shape
+    L.load()
+    gains = _gains(dev, frames, dt, q, r)
+    if out is None:
+        out = torch.empty(b, frames * dn, 3, device=dev, dtype=torch.float32)
+    elif not torch.is_tensor(out) or tuple(out.shape) != (b, frames * dn, 3) or out.dtype != torch.float32 or out.device != dev \
+            or not out.is_contiguous():
+        raise L.TcdiffError(f"smooth_x0: out must be a contiguous float32 ({b}, {frames * dn}, 3) tensor on {dev}")
+    sm = torch.empty(b, dn, frames, 2, device=dev, dtype=torch.float32) if return_smoothed else None
+    norm = (None, None)
+    if normalizer is not None:
+        scale = normalizer.scaler.scale_.detach().to("cpu", torch.float32).reshape(-1).tolist()
+        min_ = normalizer.scaler.min_.detach().to("cpu", torch.float32).reshape(-1).tolist()
+        if len(scale) != 3 or len(min_) != 3:
+            raise L.TcdiffError(f"smooth_x0: the normalizer must be fitted on 3 columns (x, y, z), got {len(scale)}")
+        norm = ((C.c_float * 3)(*scale), (C.c_float * 3)(*min_))
+    return gains, out, sm, norm
+
+
+def _handoff_launch(src, dt, gains, norm, sm, out):
+    b, dn, frames, _ = src.shape
+    s_b, s_dn, s_f, s_c = src.stride()
+    lo = src.data_ptr()
+    hi = lo + 4 * (1 + (b - 1) * s_b + (dn - 1) * s_dn + (frames - 1) * s_f + s_c)
+    if out.data_ptr() < hi and lo < out.data_ptr() + 4 * out.numel():
+        raise L.TcdiffError("smooth_x0: out overlaps the trajectories it is computed from")
+    L.check(L.load().tcdiff_nav_handoff(K._p(src), s_b, s_dn, s_f, s_c, b, dn, frames, float(dt), K._p(gains), norm[0], norm[1],
+                                        K._p(sm), K._p(out), K.stream()), "tcdiff_nav_handoff")
+    return out if sm is None else (out, sm)
+
+
+def _check_traj(x_traj, what):
+    if not torch.is_tensor(x_traj) or x_traj.dim() != 4 or x_traj.shape[-1] != 2 or min(x_traj.shape) < 1:
+        raise L.TcdiffError(f"{what}: x_traj must be a (b, dn, frames, 2) tensor, got "
+                            f"{tuple(x_traj.shape) if torch.is_tensor(x_traj) else type(x_traj).__name__}")
+    if x_traj.dtype != torch.float32:
+        raise L.TcdiffError(f"{what}: float32 trajectories only, got {x_traj.dtype}")
+    if x_traj.device.type != "cuda":
+        raise L.TcdiffError(f"{what} runs on MI355X only: move the trajectories to cuda (the CPU form is io.x0_from_navigator)")
+
+
+def smooth_x0(x_traj, *, dt=1.0, process_noise_std=1e-2, measurement_noise_std=1e-1, normalizer=None, out=None,
+              return_smoothed=False):
+    """`io.x0_from_navigator` on the device, one launch (csrc/handoff.hip): `x_traj` (b, dn, frames, 2) float32 with ANY strides
+    (read in place) -> the forward Kalman filter of `io.kalman_smooth_batch` per (clip, dancer), the state in float64 and the
+    result rounded once to float32 -> `x_0` (b, frames * dn, 3), token frame * dn + dancer, channels (x, y, 0): what
+    `ddim_sample(x_0=)` / `render_sample(x_0=)` take.  `out=` receives it (every element is written).  `return_smoothed=True`
+    returns (x_0, smoothed (b, dn, frames, 2)).  `normalizer=` (an `io.Normalizer` fitted on xyz triples) un-normalises all three
+    channels of both outputs -- the evaluation block of TrajDecoder/train_traj.py:245-259.
+
+    The gains come from `io.kalman_gains`, cached on the device per (frames, dt, process_noise_std, measurement_noise_std): from
+    the second call with the same key on there is no host-to-device copy, no allocation besides the outputs and no host
+    synchronisation.  A normalizer's six numbers are read on the host and travel as kernel arguments: keep its `scale_` / `min_`
+    host tensors (as `io.Normalizer` and the dataset make them); device-resident ones cost a copy to the host, and with it a
+    host synchronisation, per call.  `out` must not overlap `x_traj`."""
+    _check_traj(x_traj, "smooth_x0")
+    src = x_traj.detach()
+    gains, out, sm, norm = _handoff_prepare(src.shape, src.device, dt, process_noise_std, measurement_noise_std, normalizer, out,
+                                            return_smoothed)
+    return _handoff_launch(src, dt, gains, norm, sm, out)
+
+
+def rollout_x0(model: TrajDecoder, x_traj_xy, cond, step: int = 25, *, dt=1.0, process_noise_std=1e-2, measurement_noise_std=1e-1,
+               normalizer=None, out=None, return_smoothed=False):
+    """`smooth_x0(rollout(model, x_traj_xy, cond, step))` without the copy in between: the hand-off launch follows the rollout's
+    on the same stream and reads the rollout's buffer.  The gains and the outputs are made ready first, so between the rollout's
+    first launch and the hand-off's there is no clone, no torch op and no host synchronisation.  A `cond` too short for one window
+    smooths the initial window (the reference's empty range).  Keywords as `smooth_x0`."""
+    first, dev, n_windows = _rollout_check(model, x_traj_xy, cond, step)
+    b, dn = first.shape[:2]
+    frames = model.window_size + n_windows * step
+    gains, out, sm, norm = _handoff_prepare((b, dn, frames, 2), dev, dt, process_noise_std, measurement_noise_std, normalizer, out,
+                                            return_smoothed)
+    if n_windows == 0:
+        src = first.detach().to(torch.float32)
+    else:
+        src = _rollout_launch(model, first, dev, cond, step, n_windows, None)["roll"]
+    return _handoff_launch(src, dt, gains, norm, sm, out)
 
 
 # ---- training (TrajDecoder/train_traj.py) ------------------------------------------------------------------------------------------
