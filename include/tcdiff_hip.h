@@ -881,6 +881,70 @@ int tcdiff_nav_train_fwd(const tcdiff_nav_args* a, const tcdiff_nav_train_args* 
  * floating-point atomics, the same bits from the same seed.  Inputs get no gradient. */
 int tcdiff_nav_train_bwd(const tcdiff_nav_args* a, const tcdiff_nav_train_args* t, const float* wm, hipStream_t stream);
 
+/* ---- the rest of the Navigator's training step (csrc/navigator_step.hip): loss head and optimizer ----------------------------
+ * The loss of TrajDecoder/train_traj.py:183-196 on pre, tgt = (b, dn, seq, 2) fp32 DEVICE views, element (clip, dancer, frame,
+ * channel) at p[clip * strides[0] + dancer * strides[1] + frame * strides[2] + channel * strides[3]] (HOST long[4] element
+ * strides: `x[:, :, recon_start:recon_end]` is read in place, nothing is copied):
+ *   recon = mean((pre - tgt)^2)                                                      train_traj.py:183  over b dn seq 2 elements
+ *   dis   = mean(((tgt[:, 1:] - tgt[:, :-1]) - (pre[:, 1:] - pre[:, :-1]))^2)        :186-188           over b (dn - 1) seq 2
+ *   v     = mean(((tgt[:, :, 1:] - tgt[:, :, :-1]) - (pre[:, :, 1:] - ...))^2)       :191-193           over b dn (seq - 1) 2
+ *   out   = {recon + 2 dis + 2 v, recon, dis, v}                                     :196
+ * Rounding points: every difference, the difference of differences, the square and every addition round on their own (no
+ * contraction), as the reference's tensor expression; each mean is sum / count (one division); total = (recon + 2 dis) + 2 v.
+ * The sums are fixed-order and two-stage, without floating-point atomics: workgroup k sums elements [k, k + 1) *
+ * TC_NAV_LOSS_BLOCK (8 per thread in index order, then a fixed tree over the 256 threads) into partial[k][3]; a second launch of
+ * one workgroup adds the partials the same way.  Same input, same bits.
+ * partial: DEVICE workspace, 3 * ceil(b dn seq 2 / TC_NAV_LOSS_BLOCK) floats.  out: DEVICE float[4].
+ * TC_ERR_ARG for a NULL pointer, b < 1, or dn < 2 / seq < 2 (a mean over zero elements: the reference's loss is NaN there). */
+#define TC_NAV_LOSS_BLOCK 2048
+int tcdiff_nav_loss(const float* pre, const long* pre_strides, const float* tgt, const long* tgt_strides, int b, int dn, int seq,
+                    float* partial, float* out, hipStream_t stream);
+
+/* d_pre [b][dn][seq][2] (contiguous) = grad_out[0] * d total / d pre, replacing autograd through train_traj.py:183-196 below
+ * `loss.backward()` (:200), one launch, one thread per element:
+ *   d_pre = grad_out * ((c_r e + c_d (ed[d - 1] - ed[d])) + c_v (ev[s - 1] - ev[s]))
+ * with e, ed, ev the forward's three difference fields (recomputed with the forward's rounding points), the terms past either
+ * end absent, and c_r = 2 / (b dn seq 2), c_d = 4 / (b (dn - 1) seq 2), c_v = 4 / (b dn (seq - 1) 2) computed in double and
+ * rounded once.  grad_out: DEVICE float, read by the kernel (no host copy).  tgt gets no gradient.  Errors as tcdiff_nav_loss. */
+int tcdiff_nav_loss_bwd(const float* pre, const long* pre_strides, const float* tgt, const long* tgt_strides, int b, int dn,
+                        int seq, const float* grad_out, float* d_pre, hipStream_t stream);
+
+/* torch.optim.AdamW / Adam (`optimizer.step()`, train_traj.py:201; utils_model.initial_optim) over every parameter in ONE launch:
+ * a DEVICE table of chunks of <= 65536 elements, one workgroup each.  A chunk with `dst` also writes each new parameter value to
+ * its place in one of TrajDecoder's packed weight images (tcdiff_nav_args.lstm_w / lstm_bih / lstm_bhh / blocks / dec,
+ * tcdiff_nav_music_front's wm): element e = e0 + i of the parameter goes to dst[(e / row) * sr + (e % row) * sc] -- row = numel,
+ * sc = 1 for a flat copy; row = 876, sr = 880 for a zero-padded matrix; row = in, sr = 1, sc = 256 for the transposed LSTM
+ * weights.  The pad elements of an image are never written and stay zero. */
+typedef struct {
+    float* p;          /* parameter */
+    const float* g;    /* gradient */
+    float* m;          /* exp_avg */
+    float* v;          /* exp_avg_sq */
+    float* dst;        /* the parameter's image, or NULL */
+    long n;            /* elements of this chunk */
+    long e0;           /* index of the chunk's first element inside its parameter */
+    long row, sr, sc;  /* the scatter above */
+} tcdiff_nav_adamw_chunk;
+
+/* torch/optim/adam.py _single_tensor_adam's Python doubles, rounded to fp32 where they meet a tensor.  Per element:
+ *   decoupled: p = p * decay                     else: g = fma(p, wd, g)            [add(alpha=) is one fused multiply-add]
+ *   m = fma(w - 1, g - m, g) for w = omb1 >= 0.5, else fma(w, g - m, m)             [at::native::lerp]
+ *   v = v * beta2;  v = v + (omb2 * g) * g                                          [mul_, addcmul_: four roundings]
+ *   denom = sqrt(v) / bc2_sqrt + eps;  p = p + (neg_step * m) / denom               [IEEE sqrt and divisions, no contraction] */
+typedef struct {
+    float decay;       /* 1 - lr * weight_decay */
+    float wd;          /* weight_decay (the coupled form adds wd * p to the gradient) */
+    float omb1;        /* 1 - beta1 */
+    float beta2, omb2; /* beta2, 1 - beta2 */
+    float neg_step;    /* -(lr / (1 - beta1^step)) */
+    float bc2_sqrt;    /* sqrt(1 - beta2^step) */
+    float eps;
+    int decoupled;     /* 1: AdamW, 0: Adam with L2 weight decay */
+} tcdiff_nav_adamw_scalars;
+
+int tcdiff_nav_adamw(const tcdiff_nav_adamw_chunk* chunks, int n_chunks, const tcdiff_nav_adamw_scalars* scalars,
+                     hipStream_t stream);
+
 /* library identification */
 const char* tcdiff_version(void);
 

@@ -7,8 +7,8 @@ from .model import DanceDecoder  # noqa: F401
 from .diffusion import GaussianDiffusion, EMA  # noqa: F401
 from .adan import Adan  # noqa: F401
 from .fk import SMPLSkeleton, ax_from_6v  # noqa: F401
-from .navigator import TrajDecoder, TrajTrainer  # noqa: F401
+from .navigator import TrajDecoder, TrajTrainer, TrajAdamW, traj_loss  # noqa: F401
 from .dataset import AIOZDataset, process_motion  # noqa: F401
 
-__all__ = ["DanceDecoder", "GaussianDiffusion", "EMA", "Adan", "SMPLSkeleton", "ax_from_6v", "TrajDecoder", "TrajTrainer", "AIOZDataset",
-           "process_motion"]
+__all__ = ["DanceDecoder", "GaussianDiffusion", "EMA", "Adan", "SMPLSkeleton", "ax_from_6v", "TrajDecoder", "TrajTrainer", "TrajAdamW",
+           "traj_loss", "AIOZDataset", "process_motion"]

@@ -117,6 +117,13 @@ class AdanScalars(C.Structure):
         [("first", _i)]
 
 
+class NavAdamWScalars(C.Structure):
+    """tcdiff_nav_adamw_scalars (include/tcdiff_hip.h)"""
+    _fields_ = [(n, _f) for n in ("decay", "wd", "omb1", "beta2", "omb2", "neg_step", "bc2_sqrt", "eps")] + [("decoupled", _i)]
+
+
+NAV_LOSS_BLOCK = 2048            # TC_NAV_LOSS_BLOCK
+
 _SIGS = {
     "tcdiff_gemm_tile": [_i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, C.POINTER(TileEpi), _vp],
     "tcdiff_gemm_rowln": [_i, _vp, _vp, _i, _i, _i, _i, _i, C.POINTER(RowEpi), _vp],
@@ -182,6 +189,10 @@ _SIGS = {
     # training the Navigator (csrc/navigator.hip, csrc/navigator_train.hip)
     "tcdiff_nav_train_fwd": [C.POINTER(NavArgs), C.POINTER(NavTrainArgs), _vp, _vp],
     "tcdiff_nav_train_bwd": [C.POINTER(NavArgs), C.POINTER(NavTrainArgs), _vp, _vp],
+    # the rest of the Navigator's training step (csrc/navigator_step.hip)
+    "tcdiff_nav_loss": [_vp, C.POINTER(_l), _vp, C.POINTER(_l), _i, _i, _i, _vp, _vp, _vp],
+    "tcdiff_nav_loss_bwd": [_vp, C.POINTER(_l), _vp, C.POINTER(_l), _i, _i, _i, _vp, _vp, _vp],
+    "tcdiff_nav_adamw": [_vp, _i, C.POINTER(NavAdamWScalars), _vp],
 }
 
 EXPORTS = sorted(list(_SIGS) + ["tcdiff_version"])

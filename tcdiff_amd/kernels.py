@@ -346,6 +346,46 @@ def adan_step(table, scalars):
     L.check(L.load().tcdiff_adan_step(_p(table), table.shape[0], C.byref(scalars), stream()), "tcdiff_adan_step")
 
 
+# ---- the Navigator's loss head and optimizer (csrc/navigator_step.hip) -------------------------------------------------
+def _strides4(t):
+    return (C.c_long * 4)(*t.stride())
+
+
+def nav_loss_blocks(n_elements: int) -> int:
+    """workgroups of tcdiff_nav_loss's first stage = rows of its [n][3] workspace"""
+    return (n_elements + L.NAV_LOSS_BLOCK - 1) // L.NAV_LOSS_BLOCK
+
+
+def nav_loss(pre, tgt, partial, out):
+    """pre, tgt: (b, dn, seq, 2) fp32 views, read by their strides; out [4] = total, recon, dis, v"""
+    b, dn, seq, _ = pre.shape
+    L.check(L.load().tcdiff_nav_loss(_p(pre), _strides4(pre), _p(tgt), _strides4(tgt), b, dn, seq, _p(partial), _p(out),
+                                     stream()), "tcdiff_nav_loss")
+
+
+def nav_loss_bwd(pre, tgt, grad_out, d_pre):
+    b, dn, seq, _ = pre.shape
+    L.check(L.load().tcdiff_nav_loss_bwd(_p(pre), _strides4(pre), _p(tgt), _strides4(tgt), b, dn, seq, _p(grad_out), _p(d_pre),
+                                         stream()), "tcdiff_nav_loss_bwd")
+
+
+def nav_adamw_rows(p, g, m, v, dst=None):
+    """tcdiff_nav_adamw_chunk rows of one parameter; dst = (address, row, sr, sc) of its packed image, or None"""
+    d, row, sr, sc = dst if dst is not None else (0, 1, 0, 0)
+    cnt = p.numel()
+    return [(p.data_ptr() + 4 * lo, g.data_ptr() + 4 * lo, m.data_ptr() + 4 * lo, v.data_ptr() + 4 * lo, d, min(65536, cnt - lo), lo,
+             row, sr, sc) for lo in range(0, cnt, 65536)]
+
+
+def nav_adamw_table(rows, device):
+    """int64 [n_chunks, 10] device table for tcdiff_nav_adamw"""
+    return torch.tensor(rows, dtype=torch.int64, device=device).reshape(-1, 10)
+
+
+def nav_adamw(table, scalars):
+    L.check(L.load().tcdiff_nav_adamw(_p(table), table.shape[0], C.byref(scalars), stream()), "tcdiff_nav_adamw")
+
+
 # ---- training step: train-mode forward pieces and the backward pass ---------------------------------------------------
 def drop_params(p: float):
     """(threshold, scale) of the counter-hash dropout (csrc/train_common.h): keep iff hash >= floor(p * 2^32)."""

@@ -1,6 +1,7 @@
 """The Dance-Beat Navigator on the MI355X: `TrajDecoder` (TrajDecoder/model/traj_model.py:125-200) and the sliding-window
 rollout of `TCDiff.test_loop` (TCDiff.py:526-547), as HIP kernels (csrc/navigator.hip); `TrajTrainer` beside the module is the
-train-mode forward and the backward pass of TrajDecoder/train_traj.py (csrc/navigator_train.hip).
+train-mode forward and the backward pass of TrajDecoder/train_traj.py (csrc/navigator_train.hip); `traj_loss` and `TrajAdamW` are that
+step's loss head and optimizer (csrc/navigator_step.hip).
 
     traj_model = TrajDecoder(nfeats=2, trans_layer=6, window_size=100)
     traj_model.load_state_dict(ckpt["net"], strict=True)                 # the reference's checkpoint, key for key
@@ -171,6 +172,40 @@ class TrajDecoder(nn.Module):
         pk = dict(version=ver, lstm_w=lw, bih=bih, bhh=bhh, blocks=blocks, dec=dec, music=mus, pe=pe)
         self.__dict__["_packed"] = pk
         return pk
+
+    def _image_slots(self):
+        """Where `_weights()` puts every parameter: [(parameter, image, offset, row, sr, sc)] -- element e of the parameter is element
+        offset + (e // row) * sr + (e % row) * sc of the image (tcdiff_nav_adamw_chunk, include/tcdiff_hip.h).  `TrajAdamW` writes
+        through this map; tests/test_navigator_step_cpu.py holds it against `_weights()` itself."""
+        out = []
+        flat = lambda t, image, off: out.append((t, image, off, t.numel(), 0, 1))
+        for l in range(3):
+            wi, wh = getattr(self.lstm, f"weight_ih_l{l}"), getattr(self.lstm, f"weight_hh_l{l}")
+            out.append((wi, "lstm_w", l * 128 * 256, wi.shape[1], 1, 256))                 # [256][in] -> rows 0 .. in - 1, transposed
+            out.append((wh, "lstm_w", (l * 128 + 64) * 256, 64, 1, 256))                   # [256][64] -> rows 64 .. 127
+            flat(getattr(self.lstm, f"bias_ih_l{l}"), "bih", l * 256)
+            flat(getattr(self.lstm, f"bias_hh_l{l}"), "bhh", l * 256)
+        off = 0
+        for blk in self.trans_extractor.blocks:
+            a = blk.attn
+            for t in (blk.ln1.weight, blk.ln1.bias, a.query.weight, a.query.bias, a.key.weight, a.key.bias, a.value.weight,
+                      a.value.bias, a.proj.weight, a.proj.bias, blk.ln2.weight, blk.ln2.bias, blk.mlp[0].weight, blk.mlp[0].bias,
+                      blk.mlp[2].weight, blk.mlp[2].bias):
+                flat(t, "blocks", off)
+                off += t.numel()
+        d, off = self.Decoder, 0
+        for t in (d[0].weight, d[0].bias, d[2].weight, d[2].bias, d[4].weight, d[4].bias):
+            flat(t, "dec", off)
+            off += t.numel()
+        flat(d[6].weight, "dec", off)                                                      # 2 of 16 rows
+        flat(d[6].bias, "dec", off + 16 * 64)
+        m, ce, off = self.music_projection, self.trans_extractor.cond_emb, 0
+        for t, rows, ld in ((m[0].weight, 448, 880), (m[0].bias, 1, 448), (m[2].weight, 448, 448), (m[2].bias, 1, 448),
+                            (m[4].weight, 64, 448), (m[4].bias, 1, 64), (ce.weight, 64, 64), (ce.bias, 1, 64)):
+            out.append((t, "music", off, t.shape[-1], ld, 1))
+            off += rows * ld
+        assert off == _MU
+        return out
 
     # ---- workspaces ---------------------------------------------------------------------------------------------------------------
     def _plan(self, dev, b, dn, seq, pairs, roll_frames, taps):
@@ -573,3 +608,169 @@ class TrajTrainer:
                     p.grad = v
                 else:
                     p.grad.add_(v)
+
+
+# ---- the loss head (TrajDecoder/train_traj.py:183-196) -------------------------------------------------------------------------
+_LOSS_WS = {}                      # (device, workgroups) -> tcdiff_nav_loss's partial sums
+
+
+def _loss_ws(dev, n):
+    key = (str(dev), K.nav_loss_blocks(n))
+    ws = _LOSS_WS.get(key)
+    if ws is None:
+        if len(_LOSS_WS) >= 8:
+            del _LOSS_WS[next(iter(_LOSS_WS))]
+        ws = _LOSS_WS[key] = torch.empty(key[1], 3, device=dev, dtype=torch.float32)
+    return ws
+
+
+class _TrajLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pre, tgt):
+        out = torch.empty(4, device=pre.device, dtype=torch.float32)
+        K.nav_loss(pre, tgt, _loss_ws(pre.device, pre.numel()), out)
+        ctx.save_for_backward(pre, tgt)
+        ctx.set_materialize_grads(False)
+        total, parts = out[0], out[1:]
+        ctx.mark_non_differentiable(parts)
+        return total, parts
+
+    @staticmethod
+    def backward(ctx, g_total, _g_parts):
+        if g_total is None or not ctx.needs_input_grad[0]:
+            return None, None
+        pre, tgt = ctx.saved_tensors
+        if g_total.dtype != torch.float32 or g_total.device != pre.device:
+            raise L.TcdiffError("traj_loss: the incoming gradient must be a float32 scalar on the loss's device")
+        d_pre = torch.empty(pre.shape, device=pre.device, dtype=torch.float32)
+        K.nav_loss_bwd(pre, tgt, g_total, d_pre)
+        return d_pre, None
+
+
+def traj_loss(pre_traj, x_target):
+    """The loss of TrajDecoder/train_traj.py:183-196 on (b, dn, seq, 2) float32 device tensors:
+
+        total, (recon, dis, v) = traj_loss(pre_traj, x_target)        # total = recon + 2 * dis + 2 * v
+
+    `recon` is the mean squared error of the positions, `dis` that of the differences between neighbouring dancers, `v` that of the
+    frame-to-frame differences: four 0-dim views of one device tensor (the shape of `GaussianDiffusion.p_losses`' result).  `total`
+    carries ONE autograd node, whose backward is one launch writing the analytic gradient for `pre_traj`, scaled by the incoming
+    gradient read on the device; `x_target` gets none.  Both inputs may be views (`x[:, :, recon_start:recon_end]`): they are read
+    by their strides, nothing is copied.  The sums are fixed-order: the same input gives the same bits.  No host synchronisation;
+    from the second call at a shape on, no allocation besides the four scalars (forward) and the gradient (backward).
+
+    `dn == 1` or `seq == 1` raises: the reference takes a mean over zero elements there and its loss is NaN."""
+    for t, what in ((pre_traj, "pre_traj"), (x_target, "x_target")):
+        if not torch.is_tensor(t) or t.dim() != 4 or t.shape[-1] != 2 or min(t.shape) < 1:
+            raise L.TcdiffError(f"traj_loss: {what} must be a (b, dn, seq, 2) tensor, got "
+                                f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+        if t.dtype != torch.float32:
+            raise L.TcdiffError(f"traj_loss: float32 only, {what} is {t.dtype}")
+    if pre_traj.shape != x_target.shape:
+        raise L.TcdiffError(f"traj_loss: pre_traj {tuple(pre_traj.shape)} and x_target {tuple(x_target.shape)} differ in shape")
+    if pre_traj.device.type != "cuda" or x_target.device != pre_traj.device:
+        raise L.TcdiffError("traj_loss runs on MI355X only: move both tensors to one cuda device (no CPU fallback)")
+    if x_target.requires_grad:
+        raise L.TcdiffError("traj_loss: x_target gets no gradient (TrajDecoder/train_traj.py never asks for one)")
+    if pre_traj.shape[1] < 2:
+        raise L.TcdiffError("traj_loss: the dancer axis (1) has one entry: the reference's dis_loss is a mean over zero elements (NaN)")
+    if pre_traj.shape[2] < 2:
+        raise L.TcdiffError("traj_loss: the frame axis (2) has one entry: the reference's v_loss is a mean over zero elements (NaN)")
+    total, parts = _TrajLossFn.apply(pre_traj, x_target)
+    return total, (parts[0], parts[1], parts[2])
+
+
+# ---- the optimizer (TrajDecoder/train_traj.py:138,201; utils/utils_model.py initial_optim) ---------------------------------------
+class TrajAdamW(torch.optim.Optimizer):
+    """`torch.optim.AdamW` (`decoupled=False`: `torch.optim.Adam` with L2 weight decay) over the parameters of a `TrajTrainer`'s
+    net, as ONE launch per `step()` that also keeps the net's packed weight images in step:
+
+        optimizer = TrajAdamW(trainer)                                   # lr 2e-3, betas (0.5, 0.9), weight_decay 1e-6: option_traj.py
+        scheduler = torch.optim.lr_scheduler.MultiStepLR(optimizer, milestones=..., gamma=...)
+        optimizer.zero_grad(); total.backward(); optimizer.step(); scheduler.step()
+
+    One parameter group (`add_param_group` raises); `param_groups[0]` carries torch's keys and `state` torch's per-parameter `step`
+    (a host float32 scalar), `exp_avg`, `exp_avg_sq`, so `state_dict()` / `load_state_dict()` interchange with `torch.optim.AdamW` /
+    `Adam` and a run may move between the two.  `lr`, `betas`, `eps` and `weight_decay` are read from the group at every step.
+
+    `step()` updates every parameter that has a `.grad` and `requires_grad` (the others get no state, as in torch); all of them
+    must be contiguous float32 on the GPU with equal step counts.  The scalars are `_single_tensor_adam`'s Python doubles, rounded
+    to float32 where they meet a tensor, and travel as kernel arguments.  The device table of chunks points at whatever each
+    `.grad` is -- the trainer's views of its flat gradient buffer in the usual step, the caller's own tensors after accumulation
+    -- and is rebuilt only when one of its pointers changed.
+
+    The update kernel also scatters each new value into `TrajDecoder._weights()`'s images (transposed LSTM weights, zero-padded
+    music matrices, the Decoder's last linear in 2 of 16 rows), so the next forward finds them current without the torch repack.
+    `step()` then bumps the parameters' `_version`, as torch's optimizers do (the kernel wrote through raw pointers; autograd's
+    saved-tensor check stays honest), and sets the image cache's key to the new versions.  Any other change -- an in-place edit,
+    a replaced Parameter, `load_state_dict` -- still misses that key and rebuilds the images through the torch path."""
+
+    def __init__(self, trainer, lr=2e-3, betas=(0.5, 0.9), eps=1e-8, weight_decay=1e-6, decoupled=True):
+        if not isinstance(trainer, TrajTrainer):
+            raise L.TcdiffError("TrajAdamW updates the net of a navigator.TrajTrainer")
+        if not (lr >= 0.0 and eps >= 0.0 and weight_decay >= 0.0 and len(betas) == 2 and all(0.0 <= b < 1.0 for b in betas)):
+            raise L.TcdiffError(f"TrajAdamW: invalid lr / betas / eps / weight_decay: {lr}, {betas}, {eps}, {weight_decay}")
+        self.trainer, self._table, self._key = trainer, None, None
+        defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False, foreach=None,
+                        capturable=False, differentiable=False, fused=None, decoupled_weight_decay=bool(decoupled))
+        super().__init__(list(trainer.net.parameters()), defaults)
+
+    def add_param_group(self, param_group):
+        if self.param_groups:
+            raise L.TcdiffError("TrajAdamW: one parameter group only (utils_model.initial_optim's other branch names an attribute "
+                                "TrajDecoder does not have)")
+        super().add_param_group(param_group)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        if len(self.param_groups) != 1:
+            raise L.TcdiffError("TrajAdamW: one parameter group only")
+        group = self.param_groups[0]
+        if group.get("amsgrad") or group.get("maximize") or group.get("capturable") or group.get("differentiable"):
+            raise L.TcdiffError("TrajAdamW: amsgrad, maximize, capturable and differentiable are not built")
+        ps = [p for p in group["params"] if p.requires_grad and p.grad is not None]
+        if not ps:
+            return loss
+        dev = ps[0].device
+        if not all(p.device == dev and dev.type == "cuda" and p.dtype == torch.float32 and p.is_contiguous()
+                   and p.grad.device == dev and p.grad.dtype == torch.float32 and not p.grad.is_sparse and p.grad.is_contiguous()
+                   for p in ps):
+            raise L.TcdiffError("TrajAdamW.step runs on MI355X only, as one launch over contiguous float32 parameters and gradients on "
+                                "one cuda device (no CPU / per-tensor fallback)")
+        states = []
+        for p in ps:
+            st = self.state[p]
+            if len(st) == 0:
+                st["step"] = torch.tensor(0.0, dtype=torch.float32)
+                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            states.append(st)
+        steps = [float(st["step"]) for st in states]
+        if any(v != steps[0] for v in steps):
+            raise L.TcdiffError("TrajAdamW.step: the parameters' step counts differ (one launch carries one bias correction)")
+        if not all(st[k].is_contiguous() and st[k].dtype == torch.float32 and st[k].device == dev for st in states
+                   for k in ("exp_avg", "exp_avg_sq")):
+            raise L.TcdiffError("TrajAdamW.step: exp_avg / exp_avg_sq must be contiguous float32 tensors on the parameters' device")
+        net = self.trainer.net
+        wt = net._weights()                                      # current here (or rebuilt by the torch path): the kernel keeps it so
+        key = tuple(t.data_ptr() for p, st in zip(ps, states) for t in (p, p.grad, st["exp_avg"], st["exp_avg_sq"])) + \
+            tuple(wt[k].data_ptr() for k in ("lstm_w", "bih", "bhh", "blocks", "dec", "music"))
+        if key != self._key:
+            slot = {id(t): (wt[image].data_ptr() + 4 * off, row, sr, sc) for t, image, off, row, sr, sc in net._image_slots()}
+            rows = [r for p, st in zip(ps, states)
+                    for r in K.nav_adamw_rows(p, p.grad, st["exp_avg"], st["exp_avg_sq"], slot.get(id(p)))]
+            self._table, self._key = K.nav_adamw_table(rows, dev), key
+        lr, (beta1, beta2), eps, wd = float(group["lr"]), group["betas"], group["eps"], group["weight_decay"]
+        step = steps[0] + 1
+        bc1, bc2 = 1 - beta1 ** step, 1 - beta2 ** step
+        sc = L.NavAdamWScalars(decay=1 - lr * wd, wd=wd, omb1=1 - beta1, beta2=beta2, omb2=1 - beta2, neg_step=-(lr / bc1),
+                               bc2_sqrt=bc2 ** 0.5, eps=eps, decoupled=int(bool(group.get("decoupled_weight_decay", True))))
+        K.nav_adamw(self._table, sc)
+        torch.autograd.graph.increment_version(ps)
+        wt["version"] = net._weights_version()
+        torch._foreach_add_([st["step"] for st in states], 1)
+        return loss
