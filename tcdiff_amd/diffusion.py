@@ -277,13 +277,13 @@ class GaussianDiffusion(nn.Module):
         rows2 = self._prepare(B, cond, tseq, slot=0, eng=eng)[1]
         assert rows2 == rows
 
-        def step(branches: int):
-            eng.step_prologue(st, 2 * B, st["x"], B * Lq)
+        def step(branches: int, form):
+            eng.step_prologue(st, 2 * B, st["x"], B * Lq, form)
             if branches == 2:
-                out = eng.network(st["x"], B, 2, 0, B, 0, x_ready=True)
+                out = eng.network(st["x"], B, 2, 0, B, 0, x_ready=True, form=form)
                 unc, con = out, out[B * Lq:]
             else:
-                out = eng.network(st["x"], B, 1, 1, 0, B, x_ready=True)
+                out = eng.network(st["x"], B, 1, 1, 0, B, x_ready=True, form=form)
                 unc, con = None, out
             K.sampler_update(mode | L.SAMPLER_ADVANCE, unc, con, 152, st["x"], st["eps"] if step_noise is not None else None,
                              st["traj"] if traj is not None else None, None, B * Lq, nf, Lq, st["counter"],
@@ -323,19 +323,18 @@ class GaussianDiffusion(nn.Module):
                 st["qeps"].copy_(q_noise(int(t), (B, Lq, nf)).reshape(B * Lq, nf))
             # (the constraint kernel is captured reading st["cparams"] or st["params"]: part of the key -- ADVICE r5)
             ckey = None if constrain is None else (constrain["kind"], q_noise is not None, mask_rows, constrain.get("params") is not None)
-            # (the kernel form the engine resolves from its switches at every forward -- small-job layers, parts 1 + 2 merged, the
-            # fragment front, the forked prologue -- is part of the key too: a switch changed after a capture must not replay the old form)
-            split = eng._split_job(branches * B)
-            form = (split, split and eng._merge12(Lq), split and eng.front and os.environ.get("TCDIFF_SPLIT_FRONT", "1") != "0",
-                    os.environ.get("TCDIFF_FORK_PROLOGUE", "0") == "1")
+            # (the kernel form the engine resolves from its switches for every forward -- small-job layers, parts 1 + 2 merged, the
+            # fragment front, the forked prologue -- is part of the key too: a switch changed after a capture must not replay the old
+            # form.  The launches below take the SAME value, so key and launches cannot disagree.)
+            form = eng.form(branches * B)
             gkey = (mode, branches, step_noise is not None, traj is not None, clip_offset, B, gen, id(self.model), ckey, couple, u, form)
             if not use_graph:
-                step(branches)
+                step(branches, form)
             elif gkey in graphs:
                 graphs[gkey].replay()
             elif ("warm", gkey) not in graphs:
                 for _ in range(u):
-                    step(branches)              # first visit: eager (loads code objects, sets kernel attributes)
+                    step(branches, form)        # first visit: eager (loads code objects, sets kernel attributes)
                 graphs[("warm", gkey)] = True
             else:                               # second visit: capture once, replay from now on
                 for k in [k for k in graphs if is_step_key(k) and k[7] == id(self.model) and k[6] != gen]:
@@ -347,7 +346,7 @@ class GaussianDiffusion(nn.Module):
                 graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(graph):
                     for _ in range(u):
-                        step(branches)
+                        step(branches, form)
                 graphs[gkey] = graph
                 graph.replay()
             i += u

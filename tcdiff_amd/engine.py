@@ -27,8 +27,8 @@ import torch
 
 from . import _lib as L
 from . import kernels as K
+from .form import Form, resolve_form
 
-MERGE12_MAX_L = 512      # measured: profiles/r06_small_batch_split.txt
 NL_FILM = 3
 
 
@@ -61,8 +61,12 @@ class DenoiserEngine:
         self.tables_key = None
         self.film_tab = None
         self._sampler_state = None
-        self._side, self._forked = None, False     # forked stream of the step prologue's conditioning part (step_prologue)
-        self._xcur = 0                             # small-job layers (chain_split): which of b["xa"], b["xb"] holds the residual stream
+        # the one piece of state that crosses calls: step_prologue() sets _forked when it put its conditioning part on the stream
+        # _side, the network() that follows joins that stream in front of layer 0 and clears it
+        self._side, self._forked = None, False
+        self.last_form: Optional[Form] = None      # the form network() last ran (tests read it)
+        self.n_cu = torch.cuda.get_device_properties(device).multi_processor_count
+        self.skt = (self.Lseq + 31) // 32          # 32-key tiles of a sequence's self-attention K / V fragment images
         # row-block chain kernels (csrc/chain.hip): bf16 only; the f32 parity mode keeps the op-by-op kernels
         self.act = int(cfg.get("act", L.ACT_GELU))    # feed-forward activation (TC_ACT_*); the chain kernels are GELU only
         # use_rotary=False (model/model.py:441-448,564,580): identity rotary table + PositionalEncoding rows added to the motion and
@@ -332,15 +336,13 @@ class DenoiserEngine:
             b["Kf"] = z(NL, 2 * B, H, self.nkt * 2048)
             b["Vf"] = z(NL, 2 * B, H, self.nkt * 2048)
         if self.fuse_sa:                             # fragment-order Q (per 64-row block of a sequence), K, V of the next layer
-            self.skt = (Lq + 31) // 32
-            self.n_cu = torch.cuda.get_device_properties(dev).multi_processor_count
             b["Qf"] = z(2 * B * ((Lq + 15) // 16), 8, 4, 2, 64, 8)       # (block, wave)-private; enough for 16-row blocks
             # two of each: a launch reads layer l's keys in every block's prologue while its early blocks already write layer l + 1's.
             # INVARIANT the in-launch attention relies on: every V^T slot of a sequence's last 32-key tile is FINITE (keys >= L are
             # masked, but P = 0 times NaN is NaN).  The chain launch writes every slot it owns (clamped copies of the last row) and
             # zeros the one half-tile nobody owns (store_vfrag, MT = 1); the zero-fill here covers images no launch has written yet.
             b["sKf"], b["sVf"] = z(2, 2 * B, H, self.skt * 2048), z(2, 2 * B, H, self.skt * 2048)
-            if self._split_rows(2 * B, Lq):          # small jobs: second residual buffer, two partial-sum slabs (chain_split.hip)
+            if self.form(2 * B, planned=True).split:     # small jobs: second residual buffer, two partial-sum slabs (chain_split.hip)
                 nblk = 2 * B * ((Lq + 15) // 16)
                 b["xb"] = z(R, 512, dtype=torch.float32)
                 b["P0"], b["P1"] = z(nblk, 4, 16, 512, dtype=torch.float32), z(nblk, 4, 16, 512, dtype=torch.float32)
@@ -499,10 +501,10 @@ class DenoiserEngine:
             return token_rows // self.dn, self.dn * self.nf, self.kin
         return token_rows, self.nf, 192
 
-    def step_prologue(self, st: dict, n_rows_seq: int, x: torch.Tensor, rows: int):
+    def step_prologue(self, st: dict, n_rows_seq: int, x: torch.Tensor, rows: int, form: Form):
         """One sampler step's prologue in a single launch (timestep lookup, FiLM input, time-token K/V rows, model
         dtype copy of x_t, step counter bump), then the FiLM generator GEMM.  Replaces step_begin +
-        per_step_conditioning + network's convert_pad + step_end."""
+        per_step_conditioning + network's convert_pad + step_end.  form: the one the network() that follows is given."""
         dt, w, b = self.dt, self.w, self.b
         full = self.use_full
         nfilm = self.NL * NL_FILM * 1024
@@ -515,7 +517,7 @@ class DenoiserEngine:
                 n_rows_seq, self.kv_tab, self.n_t, None if full else b["Kc"], None if full else b["Vc"],
                 b["Kf"] if full else None, b["Vf"] if full else None, self.NL, b["Kc"].shape[1], self.H,
                 self.Lpc, self.nkt if full else 0, self.S, x, b["xin"], *self._xin_shape(rows))
-        if tab is not None and self.use_chain and self.front and os.environ.get("TCDIFF_FORK_PROLOGUE", "0") == "1":
+        if tab is not None and form.fork_prologue:
             # Two parts (tcdiff_step_prologue_args.parts): the x_t copy the first GEMM waits for, and -- on a forked stream, beside
             # the input / fusion GEMMs and the front launch, which leave a third of the CUs idle -- the FiLM rows and time-token rows
             # that nothing reads before layer 0's chain launch ~110 us later (network() joins there).  The fork is part of the
@@ -538,16 +540,18 @@ class DenoiserEngine:
                         out=b["film"], ldc=nfilm)
 
     def network(self, x: torch.Tensor, B: int, branches: int, kv_slot0: int, n_shared: int, film_row0: int,
-                x_ready: bool = False):
+                x_ready: bool = False, form: Optional[Form] = None):
         """DanceDecoder.forward body after the conditioning prologue (model/model.py:553-561,621-623) for
         `branches` stacked copies of the B clips in x (fp32 [B*L, nfeats]).  Returns b['out'] fp32 [branches*B*L, 152].
 
         branches=2: rows [uncond | cond]; layer-0 self-attention (which depends on x only) is evaluated once and
-        shared.  kv_slot0 / n_shared map sequences to cross-attention cache slots; film_row0 is the first FiLM row."""
+        shared.  kv_slot0 / n_shared map sequences to cross-attention cache slots; film_row0 is the first FiLM row.
+        form: the launch form of this forward when the caller has resolved it already (the sampler: it keys its graphs by it)."""
         dt, w, b = self.dt, self.w, self.b
         Lq, S, H, dn, NL = self.Lseq, self.S, self.H, self.dn, self.NL
         Rs, R = B * Lq, branches * B * Lq
         nseq = branches * B
+        form = self.last_form = self.form(nseq) if form is None else form
         fld = NL * NL_FILM * 1024
         film0 = b["film"][film_row0:]
         rope = w["rope"]
@@ -556,7 +560,7 @@ class DenoiserEngine:
             K.convert_pad(dt, x, b["xin"], *self._xin_shape(Rs))
         # small jobs (the layers in their four-workgroups-per-block form): these products through the launcher's small-M kernel too
         # -- another summation order, so only together with that kernel family (tcdiff_tile_epi.small_m)
-        sm = self._split_job(nseq)
+        sm = form.small_m
         if self.fold_in:
             K.gemm_tile(dt, b["xin"], w["f1in.w"], B * S, 1024, self.kin, bias=w["f1in.b"], act=L.ACT_RELU, out=b["f1"],
                         ldc=1024, small_m=sm)
@@ -567,8 +571,7 @@ class DenoiserEngine:
         K.gemm_tile(dt, b["f1"], w["f2.w"], B * S, 1024, 1024, bias=w["f2.b"], act=L.ACT_RELU, out=b["f2"], ldc=1024, small_m=sm)
         # last fusion linear, one group per dancer in ONE launch: group d writes token rows m*dn + d (de-interleave:
         # frame row m, dancer d -> token m*dn + d); fused with layer-0 norm1 + rotary
-        self._frag_front = self.front and self._split_job(nseq) and os.environ.get("TCDIFF_SPLIT_FRONT", "1") != "0"
-        if self._frag_front:
+        if form.frag_front:
             # SMALL jobs: the last fusion linear as one plain product -- [frames][512 dn] fp32 IS the token rows [frames dn][512] --
             # then layer 0's norm1 / rotary / Q, K, V as fragment images (tcdiff_chain_split part 0): layer 0's self-attention runs
             # inside its first launch like every other layer's.  (TC_CHAIN_FRONT has 9 workgroups for one 3 x 150 clip.)
@@ -599,12 +602,13 @@ class DenoiserEngine:
         if self._forked:                           # the conditioning part of the step prologue (step_prologue): first needed here
             torch.cuda.current_stream().wait_stream(self._side)
             self._forked = False
+        xcur = 0                                   # small-job layers: which of b["xa"], b["xb"] holds the residual stream
         for l in range(NL):
             p = f"l{l}."
             rows_sa = Rs if l == 0 else R          # layer-0 self-attention is branch-independent
             nseq_sa = B if l == 0 else nseq
             if self.use_chain:
-                self._layer_chained(l, B, branches, Kc0, Vc0, film0, fld, n_shared, kv_slot0)
+                xcur = self._layer_chained(l, form, xcur, B, branches, film0, fld, n_shared, kv_slot0)
                 continue
             # ---- self-attention block (model/model.py:326-327,374-383,71-107)
             K.gemm_tile(dt, b["rot"], w[p + "qkv.w"], rows_sa, 1536, 512, A2=b["h"], split_n=1024, mode=L.EPI_QKV_HEADS,
@@ -647,95 +651,115 @@ class DenoiserEngine:
         K.gemm_tile(dt, b["h"], w["fin.w"], R, self.nf, 512, bias=w["fin.b"], mode=L.EPI_STORE_F32, out=b["out"], ldc=152)
         return b["out"]
 
+    def form(self, nseq: int, planned: Optional[bool] = None) -> Form:
+        """The launch form of a forward over nseq sequences, resolved ONCE per forward from the constructor's switches, this chip and the
+        per-forward switches as they are now (form.py).  planned: plan() asks before the small-job workspaces exist."""
+        return resolve_form(use_chain=self.use_chain, use_full=self.use_full, front=self.front, fuse_sa=self.fuse_sa,
+                            chain_nw=self.chain_nw, nseq=nseq, Lq=self.Lseq, n_cu=self.n_cu,
+                            planned="xb" in self.b if planned is None else planned)
+
     def _split_job(self, nseq: int) -> bool:
-        """whether this forward runs the decoder layers in their small-job form (csrc/chain_split.hip)"""
-        return bool(self.use_full and self.fuse_sa and self.chain_nw == 8 and "xb" in self.b and self._split_rows(nseq, self.Lseq))
+        return self.form(nseq).split
 
-    @staticmethod
-    def _merge12(Lq: int) -> bool:
-        """parts 1 + 2 of the small-job layer as one launch (tcdiff_chain_split part 12): TCDIFF_SPLIT_MERGE=0 never, =1 always,
-        default: sequences of at most MERGE12_MAX_L tokens (every member then streams the sequence's K / V for all eight heads)"""
-        v = os.environ.get("TCDIFF_SPLIT_MERGE", "")
-        return v == "1" or (v != "0" and Lq <= MERGE12_MAX_L)
-
-    def _split_rows(self, nseq: int, Lq: int) -> bool:
-        """the small-job form of the layer (four workgroups per 16-row block): when all of them fit the chip at once"""
-        if os.environ.get("TCDIFF_SPLIT", "1") == "0" or self.chain_nw != 8 or Lq < 16:
-            return False
-        return 4 * nseq * ((Lq + 15) // 16) <= self.n_cu
-
-    def _layer_chained(self, l: int, B: int, branches: int, Kc0, Vc0, film0, fld: int, n_shared: int, kv_slot0: int):
-        """One decoder layer as attention / chain A / attention / chain B (csrc/chain.hip): the Q, K, V images of
-        this layer's self-attention were written by the previous layer's chain B (layer 0: by the QKV GEMM below)."""
-        dt, w, b = self.dt, self.w, self.b
-        Lq, S, H, NL = self.Lseq, self.S, self.H, self.NL
-        Rs, R = B * Lq, branches * B * Lq
-        nseq = branches * B
-        p = f"l{l}."
-        rope = w["rope_cb"]
+    def _layer_chained(self, l: int, form: Form, xcur: int, B: int, branches: int, film0, fld: int, n_shared: int, kv_slot0: int) -> int:
+        """One decoder layer through the chain kernels (csrc/chain.hip, chain_split.hip) in the family `form` names: the Q, K, V
+        images of its self-attention were written by the previous layer's launch (layer 0: by the front launch or the QKV GEMM
+        below).  xcur, and the value returned: which of b["xa"], b["xb"] holds the residual stream (the small-job layers move it)."""
+        dt, b, Lq, H = self.dt, self.b, self.Lseq, self.H
+        Rs, nseq = B * Lq, branches * B
+        frag0 = l == 0 and form.frag_front         # layer 0's Q / K / V came as fragment images (network())
         if l == 0 and not self.front:
-            K.gemm_tile(dt, b["rot"], w[p + "qkv.w"], Rs, 1536, 512, A2=b["h"], split_n=1024, mode=L.EPI_QKV_HEADS,
+            K.gemm_tile(dt, b["rot"], self.w["l0.qkv.w"], Rs, 1536, 512, A2=b["h"], split_n=1024, mode=L.EPI_QKV_HEADS,
                         out=b["Q"], out_k=b["K"], out_v=b["V"], scale_q=0.125, Lseq=Lq, Lp=self.Lp, H=H, n_q=512,
                         n_k=512)
-        # fused: layers 1.. compute their self-attention inside the chain launch from the fragments the previous launch wrote
-        fused = self.fuse_sa and self.chain_nw == 8
-        frag0 = l == 0 and getattr(self, "_frag_front", False)      # layer 0's Q / K / V came as fragment images (network())
-        if not (fused and l > 0) and not frag0:
+        # fused_sa: layers 1.. compute their self-attention inside the chain launch from the fragments the previous launch wrote
+        if not (form.fused_sa and l > 0) and not frag0:
             K.attention(dt, b["Q"], b["K"], b["V"], b["O"], B if l == 0 else nseq, H, Lq, Lq, self.Lp, self.Lp, 512)
-        last = l + 1 == NL
-        nn = f"l{l + 1}.norm1." if not last else None
+        head, tail = self._head_args(l, Rs, film0, fld), self._tail_args(l, form, frag0, film0)
+        x_in = self._layer_input(l, Rs, frag0, b["xa"])
+        if not self.use_full:
+            self._layer_chain_ab(l, nseq, film0, fld, n_shared, kv_slot0, head, tail, x_in)
+            return xcur
+        w, p = self.w, f"l{l}."                    # the cross-attention block inside the launch: K / V from the fragment-ordered caches
+        cross = dict(filmb=film0[:, (l * 3 + 1) * 1024:], n3_g=w[p + "norm3.g"], n3_b=w[p + "norm3.b"], kf=b["Kf"][l, kv_slot0:],
+                     vf=b["Vf"][l, kv_slot0:], n_shared=n_shared, nkt=self.nkt, Lk=self.S + 2)
+        if form.split:
+            return self._layer_split(l, form, xcur, Rs, nseq, {**head, **tail, **cross})
+        self._layer_fused(l, nseq, {**head, **tail, **cross}, x_in)
+        return xcur
+
+    def _head_args(self, l: int, Rs: int, film0, fld: int) -> dict:
+        """the self-attention block's tail in a layer launch: fc, LayerNorm + FiLM (rows pre-folded with sln / cln / ff2.b, load_weights),
+        residual add, norm2 + rotary; every launch says itself where it reads (_layer_input) and writes the stream"""
+        w, p = self.w, f"l{l}."
+        return dict(a_mod=Rs if l == 0 else 0, ln_eps=1e-6,      # (layer 0: one attention output for both branches)
+                    film=film0[:, (l * 3 + 0) * 1024:], film_ld=fld, n2_g=w[p + "norm2.g"], n2_b=w[p + "norm2.b"], n2_eps=1e-5,
+                    rope=w["rope_cb"])
+
+    def _layer_input(self, l: int, Rs: int, frag0: bool, x) -> dict:
+        """where a layer's first residual add reads the stream: layer 0 from b["xs"] -- one copy for both branches, row-major unless
+        the TC_CHAIN_FRONT launch wrote it -- every other layer from x, COLUMN-BLOCKED on this path"""
+        if l == 0:
+            return dict(xres=self.b["xs"], xres_mod=Rs, xres_rowmajor=not self.front or frag0)
+        return dict(xres=x, xres_mod=0, xres_rowmajor=False)
+
+    def _tail_args(self, l: int, form: Form, frag0: bool, film0) -> dict:
+        """the feed-forward block and what follows it in a layer launch: linear1 / linear2 + FiLM, norm4, linear3 (the last layer's: folded
+        with final_layer), the next layer's norm1 + rotary and Q, K, V -- head-major images, or with form.fused_sa fragment images,
+        which is then also how this layer's own self-attention operands come in."""
+        w, b, p = self.w, self.b, f"l{l}."
+        last = l + 1 == self.NL
+        nn = f"l{l + 1}.norm1."
         tail = dict(b1=w[p + "ff1.b"], film3=film0[:, (l * 3 + 2) * 1024:], n4_g=w[p + "norm4.g"],
                     n4_b=w[p + "norm4.b"], n4_eps=1e-5, b3=w[p + "l3out.b"] if last and self.fold_out else w[p + "l3.b"],
                     nn_g=None if last else w[nn + "g"], nn_b=None if last else w[nn + "b"], nn_eps=1e-5,
                     q_out=None if last else b["Q"], k_out=None if last else b["K"], v_out=None if last else b["V"],
                     h_out=(b["out"] if self.fold_out else b["h"]) if last else None,
-                    out_ld=152 if last and self.fold_out else 0, scale_q=0.125, Lp=self.Lp, H=H)
-        if fused:
-            # the smallest row blocks that still give every block its own CU (a block streams the layer's weights whatever its rows)
-            tail.update(seq_blocks=True, mt=next((m for m in (1, 2) if nseq * ((Lq + 16 * m - 1) // (16 * m)) <= self.n_cu), 4))
+                    out_ld=152 if last and self.fold_out else 0, scale_q=0.125, Lp=self.Lp, H=self.H)
+        if form.fused_sa:
+            tail.update(seq_blocks=True, mt=form.mt)
             if l > 0 or frag0:
                 tail.update(sa_q=b["Qf"], sa_kf=b["sKf"][l & 1], sa_vf=b["sVf"][l & 1], sa_nkt=self.skt)
             if not last:
                 tail.update(q_out=None, k_out=None, v_out=None, qf_out=b["Qf"], kf_out=b["sKf"][(l + 1) & 1],
                             vf_out=b["sVf"][(l + 1) & 1], out_nkt=self.skt)
-        head = dict(a_mod=Rs if l == 0 else 0, ln_eps=1e-6,     # (film rows: pre-folded with sln / cln / ff2.b, load_weights)
-                    film=film0[:, (l * 3 + 0) * 1024:], film_ld=fld, xres=b["xs"] if l == 0 else b["xa"],
-                    xres_mod=Rs if l == 0 else 0, xres_rowmajor=l == 0 and (not self.front or frag0), xout=b["xa"],
-                    n2_g=w[p + "norm2.g"],
-                    n2_b=w[p + "norm2.b"], n2_eps=1e-5, rope=rope)     # b["xa"] is COLUMN-BLOCKED on this path
-        if self._split_job(nseq):
-            # SMALL jobs (csrc/chain_split.hip): four workgroups per 16-row block, four launches per layer; the residual stream
-            # alternates between b["xa"] and b["xb"] (a part reads whole rows and stores quarters), the partial sums between two slabs
-            full = dict(filmb=film0[:, (l * 3 + 1) * 1024:], n3_g=w[p + "norm3.g"], n3_b=w[p + "norm3.b"], kf=b["Kf"][l, kv_slot0:],
-                        vf=b["Vf"][l, kv_slot0:], n_shared=n_shared, nkt=self.nkt, Lk=S + 2)
-            args = {**head, **tail, **full}
-            args["mt"] = 1
-            mode = L.CHAIN_FULL_LAST if last else L.CHAIN_FULL
-            X, P = (b["xa"], b["xb"]), (b["P0"], b["P1"])
-            cur = self._xcur                           # X[cur] holds this layer's input x (layer 0 reads b["xs"] instead)
-            o1 = 0 if l == 0 else cur ^ 1
-            launch = lambda part, **kw: K.chain(mode, R, Lq, b["O"], w[p + "chainF"], split_part=part, **{**args, **kw})
-            x_in = {} if l == 0 else dict(xres=X[cur])                                         # layer 0: xres = b["xs"] (head)
-            if self._merge12(Lq):
-                # short sequences: self-attention of all eight heads and the whole fc in every member, one exchange less
-                launch(12, p_out=P[1], xout=X[o1], **x_in)
-            else:
-                launch(1, p_out=P[0])
-                launch(2, p_in=P[0], p_out=P[1], xout=X[o1], **x_in)
-            flat = dict(xres_mod=0, xres_rowmajor=False)
-            launch(3, p_in=P[1], p_out=P[0], xres=X[o1], xout=X[o1 ^ 1], **flat)
-            launch(4, p_in=P[0], xres=X[o1 ^ 1], xout=X[o1], **flat)
-            self._xcur = o1
-            return
-        if self.use_full:
-            # self-attention tail, cross-attention (K / V from the fragment-ordered caches) and feed-forward in ONE launch
-            K.chain(L.CHAIN_FULL_LAST if last else L.CHAIN_FULL, R, Lq, b["O"], w[p + "chainF"],
-                    filmb=film0[:, (l * 3 + 1) * 1024:], n3_g=w[p + "norm3.g"],
-                    n3_b=w[p + "norm3.b"], kf=b["Kf"][l, kv_slot0:], vf=b["Vf"][l, kv_slot0:], n_shared=n_shared,
-                    nkt=self.nkt, Lk=S + 2, **head, **tail)
-            return
-        K.chain(L.CHAIN_A, R, Lq, b["O"], w[p + "chainA"], **head, q_out=b["Q"], scale_q=0.125, Lp=self.Lp, H=H)
-        K.attention(dt, b["Q"], Kc0[l], Vc0[l], b["O"], nseq, H, Lq, S + 2, self.Lp, self.Lpc, 512, n_shared=n_shared)
-        K.chain(L.CHAIN_B_LAST if last else L.CHAIN_B, R, Lq, b["O"], w[p + "chainB"],
-                ln_eps=1e-6, film=film0[:, (l * 3 + 1) * 1024:], film_ld=fld,
-                xres=b["xa"], xout=b["xa"], n2_g=w[p + "norm3.g"], n2_b=w[p + "norm3.b"], n2_eps=1e-5, rope=rope, **tail)
+        return tail
+
+    def _layer_split(self, l: int, form: Form, xcur: int, Rs: int, nseq: int, args: dict) -> int:
+        """SMALL jobs (csrc/chain_split.hip): four workgroups per 16-row block, four launches per layer, three with parts 1 + 2
+        merged.  A part reads whole rows of the residual stream and stores quarters, so nothing is in place: the stream alternates
+        between X = (b["xa"], b["xb"]), the partial sums between the slabs P.  Returns which of X holds the stream afterwards."""
+        b, Lq = self.b, self.Lseq
+        X, P = (b["xa"], b["xb"]), (b["P0"], b["P1"])
+        o = 0 if l == 0 else xcur ^ 1              # X[o]: behind the self-attention block and behind the layer; X[o ^ 1]: in between
+        frag0 = l == 0 and form.frag_front
+        mode = L.CHAIN_FULL_LAST if l + 1 == self.NL else L.CHAIN_FULL
+        launch = lambda part, **io: K.chain(mode, nseq * Lq, Lq, b["O"], self.w[f"l{l}.chainF"], split_part=part, **args, **io)
+        x_in = self._layer_input(l, Rs, frag0, X[xcur])
+        if form.merge12:
+            # short sequences: self-attention of all eight heads and the whole fc in every member, one exchange less
+            launch(12, p_out=P[1], **x_in, xout=X[o])
+        else:
+            # (part 1, self-attention alone, touches neither stream buffer: the launcher just wants both named)
+            launch(1, p_out=P[0], **self._layer_input(l, Rs, frag0, b["xa"]), xout=b["xa"])
+            launch(2, p_in=P[0], p_out=P[1], **x_in, xout=X[o])
+        launch(3, p_in=P[1], p_out=P[0], xres=X[o], xout=X[o ^ 1])       # cross-attention block
+        launch(4, p_in=P[0], xres=X[o ^ 1], xout=X[o])                   # feed-forward block, linear3, the next layer's Q, K, V
+        return o
+
+    def _layer_fused(self, l: int, nseq: int, args: dict, x_in: dict):
+        """self-attention tail, cross-attention (K / V from the fragment-ordered caches) and feed-forward in ONE launch"""
+        K.chain(L.CHAIN_FULL_LAST if l + 1 == self.NL else L.CHAIN_FULL, nseq * self.Lseq, self.Lseq, self.b["O"],
+                self.w[f"l{l}.chainF"], **args, **x_in, xout=self.b["xa"])
+
+    def _layer_chain_ab(self, l: int, nseq: int, film0, fld: int, n_shared: int, kv_slot0: int, head: dict, tail: dict, x_in: dict):
+        """chain A (self-attention tail, cross-attention Q), the op-by-op cross-attention, chain B (its tail, the feed-forward block)"""
+        w, b, p = self.w, self.b, f"l{l}."
+        Lq, R, last = self.Lseq, nseq * self.Lseq, l + 1 == self.NL
+        K.chain(L.CHAIN_A, R, Lq, b["O"], w[p + "chainA"], **head, **x_in, xout=b["xa"], q_out=b["Q"], scale_q=0.125, Lp=self.Lp,
+                H=self.H)
+        K.attention(self.dt, b["Q"], b["Kc"][l, kv_slot0:], b["Vc"][l, kv_slot0:], b["O"], nseq, self.H, Lq, self.S + 2, self.Lp,
+                    self.Lpc, 512, n_shared=n_shared)
+        K.chain(L.CHAIN_B_LAST if last else L.CHAIN_B, R, Lq, b["O"], w[p + "chainB"], ln_eps=1e-6,
+                film=film0[:, (l * 3 + 1) * 1024:], film_ld=fld, xres=b["xa"], xout=b["xa"], n2_g=w[p + "norm3.g"],
+                n2_b=w[p + "norm3.b"], n2_eps=1e-5, rope=w["rope_cb"], **tail)

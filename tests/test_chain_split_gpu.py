@@ -197,7 +197,7 @@ def test_small_job_network_matches_the_fused_layers(dn, S, B, monkeypatch):
             f = m(x, cond, torch.arange(B, device=DEV) * 37 + 5, cond_drop_prob=0.0)
         eng = list(m._engines.values())
         assert all(e._split_job(2 * B) == (name != "fused") for e in eng if "xb" in e.b), name
-        assert any(getattr(e, "_frag_front", False) for e in eng) == name.endswith("+front"), name
+        assert any(e.last_form is not None and e.last_form.frag_front for e in eng) == name.endswith("+front"), name
         outs[name] = (g.clone(), f.clone())
     for name in ("split", "split+front", "merged", "merged+front"):
         for nm, a, b in zip(("guided", "forward"), outs["fused"], outs[name]):
@@ -205,3 +205,83 @@ def test_small_job_network_matches_the_fused_layers(dn, S, B, monkeypatch):
             print(f"{name} vs fused ({dn}x{S}, B={B}, {nm}): max-abs {d:.2e}, mean-abs {mean:.2e}, |out| max {float(a.abs().max()):.2f}")
             assert torch.isfinite(b).all()
             assert d < 3e-2 and mean < 4e-3, (name, nm, d, mean)
+
+
+SETTINGS = (("split+front", dict(TCDIFF_SPLIT_MERGE="0")), ("merged+front", dict(TCDIFF_SPLIT_MERGE="1")),
+            ("split", dict(TCDIFF_SPLIT_FRONT="0", TCDIFF_SPLIT_MERGE="0")), ("merged", dict(TCDIFF_SPLIT_FRONT="0", TCDIFF_SPLIT_MERGE="1")),
+            ("fused", dict(TCDIFF_SPLIT="0")))
+# The launches of one network evaluation as (kernel, mode, split_part, M, small_m), recorded on an MI355X (256 CUs) BEFORE the launch
+# form became one resolved value (tcdiff_amd/form.py) and written down here from that recording.  "F" frames, "T" tokens of one
+# branch, "R" rows of both branches: the two fusion products (the input projection is folded into the first), the last fusion
+# linear + layer 0's norm1 / rotary / Q, K, V (fragment front: a small fp32 product and part 0; otherwise TC_CHAIN_FRONT and the
+# stand-alone layer-0 attention over one branch), then eight layers.
+FULL, FULL_LAST, FRONT = L.CHAIN_FULL, L.CHAIN_FULL_LAST, L.CHAIN_FRONT
+FRAG_FRONT = [("gemm_tile", L.EPI_STORE_T, None, "F", True)] * 2 + [("gemm_tile", L.EPI_STORE_F32, None, "F", True), ("chain", FRONT, 0, "T", None)]
+CHAIN_FRONT = [("gemm_tile", L.EPI_STORE_T, None, "F", True)] * 2 + [("chain", FRONT, None, "F", None), ("attention", None, None, "T", None)]
+PARTS_1234 = [("chain", FULL, 1, "R", None), ("chain", FULL, 2, "R", None), ("chain", FULL, 3, "R", None), ("chain", FULL, 4, "R", None)] * 7 + \
+    [("chain", FULL_LAST, 1, "R", None), ("chain", FULL_LAST, 2, "R", None), ("chain", FULL_LAST, 3, "R", None), ("chain", FULL_LAST, 4, "R", None)]
+PARTS_12_34 = [("chain", FULL, 12, "R", None), ("chain", FULL, 3, "R", None), ("chain", FULL, 4, "R", None)] * 7 + \
+    [("chain", FULL_LAST, 12, "R", None), ("chain", FULL_LAST, 3, "R", None), ("chain", FULL_LAST, 4, "R", None)]
+LAUNCHES = {
+    "split+front": FRAG_FRONT + PARTS_1234,
+    "merged+front": FRAG_FRONT + PARTS_12_34,
+    "split": CHAIN_FRONT + PARTS_1234,
+    "merged": CHAIN_FRONT + PARTS_12_34,
+    "fused": [("gemm_tile", L.EPI_STORE_T, None, "F", False)] * 2 + [("chain", FRONT, None, "F", None), ("attention", None, None, "T", None)]
+    + [("chain", FULL, None, "R", None)] * 7 + [("chain", FULL_LAST, None, "R", None)],
+}
+ROWS = {(2, 60, 1): dict(F=60, T=120, R=240), (2, 37, 2): dict(F=74, T=148, R=296)}      # frames B S, tokens B dn S, rows 2 B dn S
+
+
+def record_launches(monkeypatch):
+    """wrap the launchers a network evaluation goes through and record (kernel, mode, split_part, M, small_m) of every call made
+    inside DenoiserEngine.network (the conditioning in front of it makes launches of its own)"""
+    calls, inside = [], []
+    keys = dict(chain=lambda a, kw: (a[0], kw.get("split_part"), a[1], None),
+                attention=lambda a, kw: (None, None, a[5] * a[7], None),                           # n_seq * Lq rows
+                gemm_tile=lambda a, kw: (kw.get("mode", L.EPI_STORE_T), None, a[3], bool(kw.get("small_m", False))),
+                gemm_rowln=lambda a, kw: (kw["flags"], None, a[3], None),
+                step_prologue=lambda a, kw: (kw.get("parts", 0), None, a[7], None))
+
+    def wrap(name, inner):
+        def launcher(*a, **kw):
+            if inside:
+                calls.append((name,) + keys[name](a, kw))
+            return inner(*a, **kw)
+        monkeypatch.setattr(K, name, launcher)
+    for name in keys:
+        wrap(name, getattr(K, name))
+    network = E.network
+
+    def recorded_network(self, *a, **kw):
+        inside.append(True)
+        try:
+            return network(self, *a, **kw)
+        finally:
+            inside.pop()
+    monkeypatch.setattr(E, "network", recorded_network)
+    return calls
+
+
+def test_launch_sequence_of_every_small_job_setting(monkeypatch):
+    """Which launches a guided evaluation makes, in order, under the five settings of the test above, on 2 x 60, B = 1 (120-token
+    sequences: eight 16-row blocks) and on 2 x 37, B = 2 (a 10-row last block): 64 and 80 workgroups in the small-job form, which any
+    chip of 80 CUs or more takes."""
+    calls = record_launches(monkeypatch)
+    for (dn, S, B), rows in ROWS.items():
+        cond = torch.stack([O.synth_cond(c, S) for c in range(B)]).to(DEV)
+        x = torch.stack([O.synth_xT(c, dn * S) for c in range(B)]).to(DEV)
+        m = DanceDecoder(nfeats=151, seq_len=S, latent_dim=512, ff_size=1024, num_layers=8, num_heads=8, dropout=0.1,
+                         cond_feature_dim=438, activation=F.gelu, required_dancer_num=dn, compute_dtype="bf16")
+        m.load_state_dict(O.synth_state_dict(dn=dn, seq_len=S))
+        m.to(DEV).eval()
+        for name, env in SETTINGS:
+            for k in ("TCDIFF_SPLIT", "TCDIFF_SPLIT_FRONT", "TCDIFF_SPLIT_MERGE"):
+                monkeypatch.delenv(k, raising=False)
+            for k, v in env.items():
+                monkeypatch.setenv(k, v)
+            calls.clear()
+            m.guided_forward(x, cond, torch.full((B,), 640, dtype=torch.long, device=DEV), 2.0)
+            want = [(kern, mode, part, rows[M], sm) for kern, mode, part, M, sm in LAUNCHES[name]]
+            print(f"{dn} x {S}, B = {B}, {name}: {len(calls)} launches")
+            assert calls == want, (dn, S, B, name, calls)

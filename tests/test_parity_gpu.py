@@ -839,7 +839,7 @@ def test_bf16x3_c2_forward_steps_and_ddim_vs_reference_golden(golden_dir, c2_x3)
 
 
 def _split_fits(nseq, Lq=450):
-    """whether the engine picks the small-job layers for nseq sequences (engine.py _split_rows, this chip's CU count)"""
+    """whether the engine picks the small-job layers for nseq sequences (tcdiff_amd/form.py, this chip's CU count)"""
     return 4 * nseq * ((Lq + 15) // 16) <= torch.cuda.get_device_properties(DEV).multi_processor_count
 
 
