@@ -726,6 +726,40 @@ int tcdiff_motion_ingest(const float* pos, const float* q, int clips, int dn, in
                          int fit, const float* scale, const float* min_, float* feats, float* raw, float* feet, float* stats,
                          hipStream_t stream);
 
+/* ---- motion quality metrics (csrc/metrics.hip) -------------------------------------------------------------------------
+ * Sample-level physical metrics of joint positions in metres, e.g. tcdiff_pose_export's full_pose.  All arithmetic is float64 on
+ * the float32 inputs (a difference of two float32 values is exact), comparisons promote the float32 value; two launches (per
+ * frame, per sequence), no host synchronisation, no atomics, every sum in a fixed order: same input, same bits.
+ * joints (b, dn, T, 24, 3) fp32 DEVICE, element (c, d, t, j, k) at joints[c * joint_strides[0] + d * joint_strides[1] +
+ * t * joint_strides[2] + 3 j + k] (HOST long[3] element strides; the trailing 24 x 3 contiguous; read in place).
+ * contacts (optional) (b, dn, T, 4) fp32 DEVICE by contact_strides the same way, feet 7, 8, 10, 11.  beats (optional) [b][T]
+ * uint8 DEVICE, non-zero = a music beat on that motion frame.  Per clip c and dancer d, J[t][j] = joint j at frame t:
+ *   pfc [b][dn]             EDGE's physical foot contact score, unscaled: rv[t] = (J[t+1][0] - J[t][0]) / D, ra[t] =
+ *                           (rv[t+1] - rv[t]) / D (D = 1 / fps, t < T - 2) with its `up` component max(., 0); a = |ra|, A = max_t a;
+ *                           fv[t][k] = |(J[t+2][f] - J[t+1][f]) without `up`| for f = 7, 10, 8, 11;
+ *                           mean_t min(fv0, fv1) min(fv2, fv3) a[t] / A.  A == 0 -> 0; T < 3 -> NaN.
+ *   contact_slide / contact_break [b][dn], contact_frames [b][dn] (long)      only with contacts: over (t < T - 1, foot k) with
+ *                           contacts[t][k] > contact_threshold and delta = |J[t+1][f] - J[t][f]|: the mean delta, the share with
+ *                           delta >= still, the count.  A zero count gives 0 for both.
+ *   collision_rate [b]      share of (frame, unordered dancer pair) with root distance without `up` < radius; dn == 1 -> 0.
+ *   beat_align [b][dn], motion_beats [b][dn] (long)      only with beats: v[t] = mean_j |J[t+1][j] - J[t][j]| (t < N = T - 1),
+ *                           s = scipy.ndimage.gaussian_filter1d(v, sigma_smooth) (radius int(4 sigma + 0.5), weights
+ *                           exp(-x^2 / 2 sigma^2) normalised, mode "reflect" of period 2 N also where the radius exceeds N);
+ *                           motion beats M = strict interior local minima of s, |M| to motion_beats; Bailando's score
+ *                           mean over music beats m of exp(-min_M (m - .)^2 / (2 sigma_beat^2)); NaN without music or motion beats.
+ * Workspaces (DEVICE, contents undefined before and after): ws TC_METRICS_WS_PLANES * b dn T doubles, iws TC_METRICS_IWS_PLANES *
+ * b dn T ints.  Outputs DEVICE double / long; those of an absent input are not written and may be NULL.
+ * TC_ERR_ARG for a NULL required pointer, b, dn or T < 1, up outside 0..2, fps, sigma_smooth or sigma_beat not > 0;
+ * TC_ERR_UNSUPPORTED for a filter radius above TC_METRICS_MAX_RADIUS. */
+#define TC_METRICS_WS_PLANES 11
+#define TC_METRICS_IWS_PLANES 3
+#define TC_METRICS_MAX_RADIUS 512
+int tcdiff_motion_metrics(const float* joints, const long* joint_strides, const float* contacts, const long* contact_strides,
+                          const unsigned char* beats, int b, int dn, int T, int up, double fps, double contact_threshold,
+                          double still, double radius, double sigma_smooth, double sigma_beat, double* ws, int* iws, double* pfc,
+                          double* contact_slide, double* contact_break, long* contact_frames, double* collision_rate,
+                          double* beat_align, long* motion_beats, hipStream_t stream);
+
 /* ---- Dance-Beat Navigator (csrc/navigator.hip) -----------------------------------------------------------------------
  * TrajDecoder (TrajDecoder/model/traj_model.py:125-200: latent_dim 64, 4 heads, nfeats 2) and the sliding-window rollout of
  * TCDiff.test_loop (TCDiff.py:526-547), exact fp32 throughout (v_mfma_f32_16x16x4_f32 products).  All pointers DEVICE fp32.

@@ -9,6 +9,7 @@ from .adan import Adan  # noqa: F401
 from .fk import SMPLSkeleton, ax_from_6v  # noqa: F401
 from .navigator import TrajDecoder, TrajTrainer, TrajAdamW, traj_loss  # noqa: F401
 from .dataset import AIOZDataset, process_motion  # noqa: F401
+from .metrics import motion_metrics, beats_from_cond, evaluate_samples, summarize  # noqa: F401
 
 __all__ = ["DanceDecoder", "GaussianDiffusion", "EMA", "Adan", "SMPLSkeleton", "ax_from_6v", "TrajDecoder", "TrajTrainer", "TrajAdamW",
-           "traj_loss", "AIOZDataset", "process_motion"]
+           "traj_loss", "AIOZDataset", "process_motion", "motion_metrics", "beats_from_cond", "evaluate_samples", "summarize"]

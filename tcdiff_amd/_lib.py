@@ -123,6 +123,7 @@ class NavAdamWScalars(C.Structure):
 
 
 NAV_LOSS_BLOCK = 2048            # TC_NAV_LOSS_BLOCK
+METRICS_WS_PLANES, METRICS_IWS_PLANES, METRICS_MAX_RADIUS = 11, 3, 512      # TC_METRICS_*
 
 _SIGS = {
     "tcdiff_gemm_tile": [_i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, C.POINTER(TileEpi), _vp],
@@ -181,6 +182,8 @@ _SIGS = {
     "tcdiff_pose_export": [_vp, _i, _i, _i, _i, _vp, _vp, _vp, C.POINTER(_i), C.POINTER(_f), _vp, _vp, _vp, _vp, _vp],
     # motion ingest (csrc/ingest.hip)
     "tcdiff_motion_ingest": [_vp, _vp, _i, _i, _i, C.POINTER(_i), C.POINTER(_f), _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    # motion quality metrics (csrc/metrics.hip)
+    "tcdiff_motion_metrics": [_vp, C.POINTER(_l), _vp, C.POINTER(_l), _vp, _i, _i, _i, _i] + [C.c_double] * 6 + [_vp] * 10,
     # Dance-Beat Navigator (csrc/navigator.hip)
     "tcdiff_nav_music_front": [_vp, _i, _i, _vp, _vp, _vp, _vp],
     "tcdiff_nav_rollout": [C.POINTER(NavArgs), _i, _vp],

@@ -550,3 +550,16 @@ def motion_ingest(pos, q, clips, dn, sq, parents, offsets, fit, scale, min_, fea
     off = (C.c_float * 72)(*[float(v) for row in offsets for v in row])
     L.check(L.load().tcdiff_motion_ingest(_p(pos), _p(q), clips, dn, sq, par, off, int(bool(fit)), _p(scale), _p(min_), _p(feats),
                                           _p(raw), _p(feet), _p(stats), stream()), "tcdiff_motion_ingest")
+
+
+# ---- motion quality metrics ----------------------------------------------------------------------------------------------
+def motion_metrics(joints, contacts, beats, up, fps, contact_threshold, still, radius, sigma_smooth, sigma_beat, ws, iws, pfc,
+                   contact_slide, contact_break, contact_frames, collision_rate, beat_align, motion_beats):
+    """joints (b, dn, T, 24, 3) / contacts (b, dn, T, 4) fp32 views, read by their strides; beats (b, T) uint8 contiguous"""
+    b, dn, T = joints.shape[:3]
+    js = (C.c_long * 3)(*joints.stride()[:3])
+    cs = None if contacts is None else (C.c_long * 3)(*contacts.stride()[:3])
+    L.check(L.load().tcdiff_motion_metrics(_p(joints), js, _p(contacts), cs, _p(beats), b, dn, T, up, fps, contact_threshold, still,
+                                           radius, sigma_smooth, sigma_beat, _p(ws), _p(iws), _p(pfc), _p(contact_slide),
+                                           _p(contact_break), _p(contact_frames), _p(collision_rate), _p(beat_align),
+                                           _p(motion_beats), stream()), "tcdiff_motion_metrics")
