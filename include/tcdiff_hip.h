@@ -760,6 +760,70 @@ int tcdiff_motion_metrics(const float* joints, const long* joint_strides, const 
                           double* contact_slide, double* contact_break, long* contact_frames, double* collision_rate,
                           double* beat_align, long* motion_beats, hipStream_t stream);
 
+/* ---- stick-figure frames (csrc/draw.hip) -----------------------------------------------------------------------------------
+ * What skeleton_render (vis.py:223-327) shows of a generated dance -- 23 bones per dancer, the root's trail on the floor and
+ * four foot markers -- as RGB frames, in two launches for any number of clips: no host synchronisation, no atomics, a fixed
+ * paint order, so the same input gives the same bits.
+ *
+ * tcdiff_draw_project, one workgroup per (clip, frame).  joints (b, dn, T, 24, 3) / contacts (optional, (b, dn, T, 4)) fp32
+ * DEVICE, read in place through joint_strides / contact_strides (HOST long[3] element strides, the trailing 24 x 3 / 4
+ * contiguous) exactly as tcdiff_motion_metrics reads them.  view (HOST float[12]): a row-major 3 x 4 matrix whose rows give
+ * screen x (pixels), screen y (pixels, down) and depth (larger = farther) of (X, Y, Z, 1); every product row . (X, Y, Z, 1) is
+ * the float32 chain fma(m2, Z, fma(m1, Y, fma(m0, X, m3))), within 3 * 2^-24 * (|m0 X| + |m1 Y| + |m2 Z| + |m3|) of its exact
+ * value.  Outputs (DEVICE):
+ *   pts [b][T][dn][24][3] fp32   screen x, screen y and depth of every joint
+ *   trail [b][T][dn][2] fp32     screen x, y of the root with its `up` component (0, 1 or 2) replaced by `floor`
+ *   order [b][T][dn] int32       painter's order of the frame's dancers: far to near by the root's depth, ties by dancer index;
+ *                                dancer d stands at rank #{e : depth_e > depth_d or (depth_e == depth_d and e < d)}; a NaN depth
+ *                                counts as +infinity
+ *   planted [b][T][dn][4] uint8  feet 7, 8, 10, 11: with contacts, contacts[t][k] > contact_threshold; without,
+ *                                |J[t+1][f] - J[t][f]| < still in float64 on the float32 joints and 1 on the last frame -- the rule
+ *                                the dataset labels with (dataset/group_dataset.py:204-207) and skeleton_render intends (:272-278)
+ * TC_ERR_ARG for a NULL pointer (contacts and contact_strides excepted; contacts without contact_strides is refused), b, dn or
+ * T < 1, up outside 0..2; TC_ERR_UNSUPPORTED for b * T above 2^31 - 1.
+ *
+ * tcdiff_draw_raster, grid (tiles, T, clips), one workgroup per 32 x 32 tile of one frame, writes frames [b][T][H][W][3] uint8
+ * RGB and nothing else.  THE PICTURE.  A pixel starts as style->background (c = the 0..255 value per channel) and the frame's
+ * primitives are blended over it in this order:
+ *   1. static_segs [n_static][4] (DEVICE fp32 ax, ay, bx, by in pixels; may be NULL when n_static == 0), the same in every
+ *      frame, in index order, colour static_rgb, half-width static_hw, opacity static_alpha;
+ *   2. per dancer d in index order, the trail segments trail[t'-1][d] -> trail[t'][d] for t' = max(1, t - trail_len + 1) .. t
+ *      (trail_len <= 0: t' = 1 .. t, every frame so far, as the reference's line 0, vis.py:163-166), colour
+ *      colors[d % n_colors], half-width trail_hw, opacity trail_alpha;
+ *   3. per dancer d = order[t][0], order[t][1], ...: the 23 bones pts[i] -> pts[parents[i]], i = 1 .. 23 in index order, colour
+ *      colors[d % n_colors], half-width line_hw, opacity 1; then, if style->markers, four discs of radius marker_radius at
+ *      joints 7, 8, 10, 11, planted_rgb where planted and free_rgb otherwise, opacity 1.
+ * A primitive is a segment (a, b) with half-width hw and opacity alpha; a disc is a segment with a == b.  Its coverage at the
+ * pixel centre p = (x + 0.5, y + 0.5) is
+ *     cov = clamp(hw + 0.5 - dist(p, segment), 0, 1) * alpha,    dist(p, segment) = |p - (a + u (b - a))|,
+ *     u = clamp((p - a) . (b - a) / |b - a|^2, 0, 1), and u = 0 for a segment of zero length,
+ * a layer blends as c += cov * (src - c) per channel, and the stored byte is (uint8)(c + 0.5).  Only screen x and y of pts are
+ * read; depth acts through `order` alone.  A primitive with a non-finite coordinate, or of a dancer index in `order` outside
+ * [0, dn), is not drawn.  The kernel evaluates all of this in float64 on the float32 inputs.
+ * CULLING.  The workgroup enumerates the primitives 256 at a time, drops those whose bounding box grown by hw + 0.5 (+ 1 / 64
+ * pixel) misses the tile's pixel centres -- their coverage is 0 on the whole tile -- and compacts the rest into LDS in paint
+ * order; the picture is bit for bit the one without culling, for any number of primitives per frame.  W and H need not be
+ * multiples of the tile; joints may lie anywhere off the image.
+ * colors (DEVICE uint8 [n_colors][3]); parents (HOST int[24], parents[0] unused); style (HOST).
+ * TC_ERR_ARG for a NULL required pointer, b, dn, T, W or H < 1, n_colors < 1, n_static < 0 (or > 0 with NULL static_segs), a
+ * parents[i] (i >= 1) outside 0..23, a half-width / radius outside [0, 16384] or an opacity outside [0, 1];
+ * TC_ERR_UNSUPPORTED for T or b above 65535 or more than 2^31 primitives in a frame. */
+typedef struct {
+    unsigned char background[3], static_rgb[3], planted_rgb[3], free_rgb[3];
+    float static_hw, static_alpha;       /* the static segments (the floor grid) */
+    float line_hw;                       /* bones */
+    float trail_hw, trail_alpha;
+    int trail_len;                       /* trail segments kept per dancer; <= 0: all */
+    int markers;                         /* non-zero: draw the foot discs */
+    float marker_radius;
+} tcdiff_draw_style;
+int tcdiff_draw_project(const float* joints, const long* joint_strides, const float* contacts, const long* contact_strides, int b,
+                        int dn, int T, const float* view, float floor, int up, double contact_threshold, double still, float* pts,
+                        float* trail, int* order, unsigned char* planted, hipStream_t stream);
+int tcdiff_draw_raster(const float* pts, const float* trail, const int* order, const unsigned char* planted, int b, int dn, int T,
+                       int W, int H, const int* parents, const float* static_segs, int n_static, const unsigned char* colors,
+                       int n_colors, const tcdiff_draw_style* style, unsigned char* frames, hipStream_t stream);
+
 /* ---- Dance-Beat Navigator (csrc/navigator.hip) -----------------------------------------------------------------------
  * TrajDecoder (TrajDecoder/model/traj_model.py:125-200: latent_dim 64, 4 heads, nfeats 2) and the sliding-window rollout of
  * TCDiff.test_loop (TCDiff.py:526-547), exact fp32 throughout (v_mfma_f32_16x16x4_f32 products).  All pointers DEVICE fp32.

@@ -122,6 +122,13 @@ class NavAdamWScalars(C.Structure):
     _fields_ = [(n, _f) for n in ("decay", "wd", "omb1", "beta2", "omb2", "neg_step", "bc2_sqrt", "eps")] + [("decoupled", _i)]
 
 
+class DrawStyle(C.Structure):
+    """tcdiff_draw_style (include/tcdiff_hip.h): colours, widths and opacities of tcdiff_draw_raster's primitives."""
+    _fields_ = [(n, C.c_ubyte * 3) for n in ("background", "static_rgb", "planted_rgb", "free_rgb")] + \
+        [("static_hw", _f), ("static_alpha", _f), ("line_hw", _f), ("trail_hw", _f), ("trail_alpha", _f), ("trail_len", _i),
+         ("markers", _i), ("marker_radius", _f)]
+
+
 NAV_LOSS_BLOCK = 2048            # TC_NAV_LOSS_BLOCK
 METRICS_WS_PLANES, METRICS_IWS_PLANES, METRICS_MAX_RADIUS = 11, 3, 512      # TC_METRICS_*
 
@@ -184,6 +191,10 @@ _SIGS = {
     "tcdiff_motion_ingest": [_vp, _vp, _i, _i, _i, C.POINTER(_i), C.POINTER(_f), _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     # motion quality metrics (csrc/metrics.hip)
     "tcdiff_motion_metrics": [_vp, C.POINTER(_l), _vp, C.POINTER(_l), _vp, _i, _i, _i, _i] + [C.c_double] * 6 + [_vp] * 10,
+    # stick-figure frames (csrc/draw.hip)
+    "tcdiff_draw_project": [_vp, C.POINTER(_l), _vp, C.POINTER(_l), _i, _i, _i, C.POINTER(_f), _f, _i, C.c_double, C.c_double, _vp, _vp,
+                            _vp, _vp, _vp],
+    "tcdiff_draw_raster": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, C.POINTER(_i), _vp, _i, _vp, _i, C.POINTER(DrawStyle), _vp, _vp],
     # Dance-Beat Navigator (csrc/navigator.hip)
     "tcdiff_nav_music_front": [_vp, _i, _i, _vp, _vp, _vp, _vp],
     "tcdiff_nav_rollout": [C.POINTER(NavArgs), _i, _vp],

@@ -716,23 +716,32 @@ class GaussianDiffusion(nn.Module):
     @torch.no_grad()
     def render_sample(self, shape, cond, normalizer=None, epoch=None, render_out=None, fk_out=None, name=None,
                       sound=True, mode="normal", noise=None, constraint=None, sound_folder="ood_sliced",
-                      start_point=None, render=True, required_dancer_num=4, x_0=None, render_len=512):
+                      start_point=None, render=True, required_dancer_num=4, x_0=None, render_len=512, *, draw_out=None):
         """Mode dispatch of the reference (model/diffusion.py:784-806); a tensor ``shape`` is taken as the samples.
 
         With a ``normalizer`` and an ``fk_out`` directory, the post-processing of model/diffusion.py:811-988 follows:
         un-normalise, 6-D -> axis-angle, the window stitch in "long" mode, SMPL FK -- one HIP launch
         (tcdiff_amd/export.py) -- and the reference's pickles: one ``{epoch}_{num}_{clip}.pkl`` per clip in "normal",
         "inpaint" and "ctrl" mode, one ``{epoch}_{song}.pkl`` per song in "long" mode, each holding ``smpl_poses``,
-        ``smpl_trans`` and ``full_pose``.  The matplotlib / ffmpeg drawing (``skeleton_render``) is not built: nothing is
-        drawn, and ``render_out``, ``sound``, ``sound_folder``, ``render`` and ``render_len`` are unused.  The samples are
-        returned either way (the reference returns None)."""
+        ``smpl_trans`` and ``full_pose``.
+
+        With a ``normalizer`` and a ``draw_out`` directory (keyword only), what was exported is also drawn, on the device
+        (tcdiff_amd/draw.py: the bones, floor trail and foot markers of ``skeleton_render``, vis.py:223-327, by a HIP
+        rasteriser instead of matplotlib) and written as animated PNGs, clip by clip: ``e{epoch}_b{num}_{clip}.png`` per clip,
+        or ``{epoch}_{song}.png`` of the song's first ``render_len`` frames in "long" mode -- the reference's names with the new
+        extension.  No audio is muxed.  ``render_out``, ``sound``, ``sound_folder`` and ``render`` are unused: without
+        ``draw_out`` nothing is drawn.  The samples are returned either way (the reference returns None)."""
         samples = self._render_samples(shape, cond, mode, noise, constraint, start_point, x_0)
-        if normalizer is not None and fk_out is not None:
+        if normalizer is not None and (fk_out is not None or draw_out is not None):
             from .export import export_poses, write_fk_out
             x = samples if samples.is_cuda else samples.to(self._device())
             parents, offsets = self._skeleton(x.device)
-            q, pos, poses, _ = export_poses(x, normalizer, mode, required_dancer_num, parents=parents, offsets=offsets)
-            write_fk_out(fk_out, mode, epoch, name, q, pos, poses)
+            q, pos, poses, contacts = export_poses(x, normalizer, mode, required_dancer_num, parents=parents, offsets=offsets)
+            if fk_out is not None:
+                write_fk_out(fk_out, mode, epoch, name, q, pos, poses)
+            if draw_out is not None:
+                from .draw import write_draw_out
+                write_draw_out(draw_out, mode, epoch, name, poses, contacts, render_len=render_len, parents=parents)
         return samples
 
     def _render_samples(self, shape, cond, mode, noise, constraint, start_point, x_0):

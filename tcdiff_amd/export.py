@@ -6,7 +6,7 @@ samples -> un-normalised SMPL axis-angle poses, root translations, FK joint posi
 * ``write_fk_out`` writes the reference's files: one ``{epoch}_{num}_{clip}.pkl`` per clip (model/diffusion.py:971-987) or one
   ``{epoch}_{song}.pkl`` per song in long mode (:930-939), each ``{"smpl_poses": (., 72), "smpl_trans": (., 3),
   "full_pose": (dn, frames, 24, 3)}`` of float32 numpy arrays.
-The matplotlib / ffmpeg drawing (``skeleton_render``) is not part of this.
+The stick-figure drawing of ``skeleton_render`` is tcdiff_amd/draw.py, which draws these joints on the device.
 """
 from __future__ import annotations
 

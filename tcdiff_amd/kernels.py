@@ -563,3 +563,23 @@ def motion_metrics(joints, contacts, beats, up, fps, contact_threshold, still, r
                                            radius, sigma_smooth, sigma_beat, _p(ws), _p(iws), _p(pfc), _p(contact_slide),
                                            _p(contact_break), _p(contact_frames), _p(collision_rate), _p(beat_align),
                                            _p(motion_beats), stream()), "tcdiff_motion_metrics")
+
+
+# ---- stick-figure frames ---------------------------------------------------------------------------------------------------
+def draw_project(joints, contacts, view, floor, up, contact_threshold, still, pts, trail, order, planted):
+    """joints (b, dn, T, 24, 3) / contacts (b, dn, T, 4) fp32 views, read by their strides; view: 12 floats (row-major 3 x 4)"""
+    b, dn, T = joints.shape[:3]
+    js = (C.c_long * 3)(*joints.stride()[:3])
+    cs = None if contacts is None else (C.c_long * 3)(*contacts.stride()[:3])
+    v = None if view is None else (C.c_float * 12)(*[float(x) for x in view])
+    L.check(L.load().tcdiff_draw_project(_p(joints), js, _p(contacts), cs, b, dn, T, v, floor, up, contact_threshold, still, _p(pts),
+                                         _p(trail), _p(order), _p(planted), stream()), "tcdiff_draw_project")
+
+
+def draw_raster(pts, trail, order, planted, b, dn, T, W, H, parents, static_segs, n_static, colors, n_colors, style, frames):
+    """style: an _lib.DrawStyle; frames: a uint8 tensor or a device address (frames placed inside a larger buffer)"""
+    par = None if parents is None else (C.c_int * 24)(*[int(p) for p in parents])
+    out = frames if frames is None or isinstance(frames, int) else frames.data_ptr()
+    L.check(L.load().tcdiff_draw_raster(_p(pts), _p(trail), _p(order), _p(planted), b, dn, T, W, H, par, _p(static_segs), n_static,
+                                        _p(colors), n_colors, None if style is None else C.byref(style), out, stream()),
+            "tcdiff_draw_raster")
