@@ -760,6 +760,53 @@ int tcdiff_motion_metrics(const float* joints, const long* joint_strides, const 
                           double* contact_slide, double* contact_break, long* contact_frames, double* collision_rate,
                           double* beat_align, long* motion_beats, hipStream_t stream);
 
+/* ---- set-level metrics (csrc/set_metrics.hip) ------------------------------------------------------------------------------
+ * Bailando's kinetic features of joint positions, and FID_k / Div_k of a set of feature rows against a reference set.  float64
+ * arithmetic on the inputs, no contraction, no atomics, no host synchronisation (tcdiff_set_check excepted: that is its purpose);
+ * every sum over frames or rows is taken as: thread i of 256 adds elements i, i + 256, ... in index order, then a fixed tree;
+ * sums over the D columns run in index order.  Same input, same bits.
+ *
+ * tcdiff_kinetic_features, one launch.  joints (b, dn, T, 24, 3) fp32 DEVICE read in place through joint_strides exactly as
+ * tcdiff_motion_metrics reads it.  feats [b][dn][72] double DEVICE, column 3 j + k of joint j.  With D = 1 / fps, w = window,
+ * d[t] = J[t][j] - J[t-1][j] (exact in float64), per frame i = 1 .. T - 1:
+ *   v_i = (sum of d[s] over s = i - w .. i + w with s - 1 >= 0 and s <= T - 1, ascending) / (count * D)
+ *   a_i = (sum of (d[s+1] - d[s]) / D^2 over s = i - w .. i + w with s - 1 >= 0 and s + 1 <= T - 1, ascending) / count
+ *   k = 0: mean_i |v_i without its `up` component|^2;  k = 1: mean_i (the `up` component of v_i)^2;  k = 2: mean_i |a_i|,
+ * mean_i = the sum over the T - 1 frames divided by T - 1.  T < 3: all 72 values NaN.
+ * TC_ERR_ARG for a NULL pointer, b, dn or T < 1, up outside 0..2, window < 1 (an acceleration window would be empty at the last
+ * frame) or fps not > 0.
+ *
+ * tcdiff_set_stats, two launches.  feats [N][D] double DEVICE, N >= 2, 1 <= D <= TC_SET_MAX_D.
+ *   fit != 0: mean[c] = sum_n x[n][c] / N and std[c] = sqrt(sum_n (x[n][c] - mean[c])^2 / N) are WRITTEN; fit == 0: they are READ.
+ *   z[c][n] = (x[n][c] - mean[c]) / (std[c] + 1e-10);  mu[c] = sum_n z[c][n] / N;  zc[c][n] = z[c][n] - mu[c]  (both [D][N], workspaces
+ *   that tcdiff_set_scores does not need);  cov[i][j] = cov[j][i] = sum_n zc[i][n] zc[j][n] / (N - 1), [D][D].
+ *   div_rows (optional, [N]): div_rows[i] = sum_{j > i} |z[.][i] - z[.][j]|, the squares added over the columns in index order.
+ * TC_ERR_ARG for a NULL pointer (div_rows excepted), N < 2 or D < 1; TC_ERR_UNSUPPORTED for D > TC_SET_MAX_D.
+ *
+ * tcdiff_set_scores, one launch of one workgroup.  ref_mu [D], ref_cov [D][D] (S1), mu, cov (S2) and div_rows [M] as
+ * tcdiff_set_stats leaves them.  div[0] = sum_i div_rows[i] / (M (M - 1) / 2).
+ *   fid[0] = |mu - ref_mu|^2 + tr S1 + tr S2 - 2 sum_i r(l_i):  S1 = V diag(w) V^T,  R = V diag(r(w)) V^T,  l = the eigenvalues of
+ *   (R S2 R + its transpose) / 2,  r(x) = sqrt(x) if x > D 2^-52 max(x_max, 0) else 0, x_max the largest eigenvalue of that
+ *   decomposition.  Both decompositions: Jacobi rotations in round-robin order (D rounded up to even; that many minus one steps of
+ *   disjoint pairs per sweep), all angles of a step taken from the matrix before it, column rotations, then row rotations, then the
+ *   rotated 2 x 2 blocks in closed form; a pair with |a_pq| <= 2^-60 sqrt(|a_pp a_qq|) is left alone; a sweep without a rotation
+ *   ends it.  Three D x (D | 1) double matrices live in LDS: 3 * 72 * 73 * 8 = 126144 bytes at D = 72, the limit TC_SET_MAX_D.
+ *   status (DEVICE int[3]): {failed, sweeps of the first decomposition, of the second}, a sweep count -1 where max_sweeps
+ *   (1 .. TC_SET_MAX_SWEEPS) sweeps all rotated; then failed = 1 and fid[0] = NaN.
+ * TC_ERR_ARG for a NULL pointer, M < 2, D < 1 or max_sweeps outside 1 .. TC_SET_MAX_SWEEPS; TC_ERR_UNSUPPORTED for D > TC_SET_MAX_D.
+ *
+ * tcdiff_set_check copies status to the host, WAITS for the stream and returns TC_ERR_NOCONVERGE if failed is set. */
+#define TC_SET_MAX_D 72
+#define TC_SET_MAX_SWEEPS 30
+#define TC_ERR_NOCONVERGE (-5)
+int tcdiff_kinetic_features(const float* joints, const long* joint_strides, int b, int dn, int T, int up, int window, double fps,
+                            double* feats, hipStream_t stream);
+int tcdiff_set_stats(const double* feats, long N, int D, int fit, double* mean, double* std_, double* z, double* zc, double* mu,
+                     double* cov, double* div_rows, hipStream_t stream);
+int tcdiff_set_scores(const double* ref_mu, const double* ref_cov, const double* mu, const double* cov, const double* div_rows,
+                      long M, int D, int max_sweeps, double* fid, double* div, int* status, hipStream_t stream);
+int tcdiff_set_check(const int* status, hipStream_t stream);
+
 /* ---- stick-figure frames (csrc/draw.hip) -----------------------------------------------------------------------------------
  * What skeleton_render (vis.py:223-327) shows of a generated dance -- 23 bones per dancer, the root's trail on the floor and
  * four foot markers -- as RGB frames, in two launches for any number of clips: no host synchronisation, no atomics, a fixed

@@ -131,6 +131,7 @@ class DrawStyle(C.Structure):
 
 NAV_LOSS_BLOCK = 2048            # TC_NAV_LOSS_BLOCK
 METRICS_WS_PLANES, METRICS_IWS_PLANES, METRICS_MAX_RADIUS = 11, 3, 512      # TC_METRICS_*
+SET_MAX_D, SET_MAX_SWEEPS = 72, 30      # TC_SET_*
 
 _SIGS = {
     "tcdiff_gemm_tile": [_i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, C.POINTER(TileEpi), _vp],
@@ -191,6 +192,11 @@ _SIGS = {
     "tcdiff_motion_ingest": [_vp, _vp, _i, _i, _i, C.POINTER(_i), C.POINTER(_f), _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     # motion quality metrics (csrc/metrics.hip)
     "tcdiff_motion_metrics": [_vp, C.POINTER(_l), _vp, C.POINTER(_l), _vp, _i, _i, _i, _i] + [C.c_double] * 6 + [_vp] * 10,
+    # set-level metrics (csrc/set_metrics.hip)
+    "tcdiff_kinetic_features": [_vp, C.POINTER(_l), _i, _i, _i, _i, _i, C.c_double, _vp, _vp],
+    "tcdiff_set_stats": [_vp, _l, _i, _i] + [_vp] * 8,
+    "tcdiff_set_scores": [_vp, _vp, _vp, _vp, _vp, _l, _i, _i, _vp, _vp, _vp, _vp],
+    "tcdiff_set_check": [_vp, _vp],
     # stick-figure frames (csrc/draw.hip)
     "tcdiff_draw_project": [_vp, C.POINTER(_l), _vp, C.POINTER(_l), _i, _i, _i, C.POINTER(_f), _f, _i, C.c_double, C.c_double, _vp, _vp,
                             _vp, _vp, _vp],
@@ -258,7 +264,7 @@ def load():
 
 
 _ERR = {-1: "invalid argument", -2: "misaligned pointer / leading dimension", -3: "kernel launch failed",
-        -4: "unsupported configuration"}
+        -4: "unsupported configuration", -5: "the eigen-solver did not converge"}
 
 
 def check(rc: int, what: str):

@@ -565,6 +565,32 @@ def motion_metrics(joints, contacts, beats, up, fps, contact_threshold, still, r
                                            _p(motion_beats), stream()), "tcdiff_motion_metrics")
 
 
+# ---- set-level metrics -----------------------------------------------------------------------------------------------------
+def kinetic_features(joints, up, window, fps, feats):
+    """joints (b, dn, T, 24, 3) fp32 view, read by its strides; feats (b, dn, 72) float64 contiguous"""
+    b, dn, T = joints.shape[:3]
+    js = (C.c_long * 3)(*joints.stride()[:3])
+    L.check(L.load().tcdiff_kinetic_features(_p(joints), js, b, dn, T, up, window, fps, _p(feats), stream()),
+            "tcdiff_kinetic_features")
+
+
+def set_stats(feats, fit, mean, std, z, zc, mu, cov, div_rows):
+    """feats (N, D) float64 contiguous; fit: mean / std are written, else read; z, zc (D, N) workspaces; div_rows (N,) or None"""
+    N, D = feats.shape
+    L.check(L.load().tcdiff_set_stats(_p(feats), N, D, int(bool(fit)), _p(mean), _p(std), _p(z), _p(zc), _p(mu), _p(cov),
+                                      _p(div_rows), stream()), "tcdiff_set_stats")
+
+
+def set_scores(ref_mu, ref_cov, mu, cov, div_rows, max_sweeps, fid, div, status):
+    L.check(L.load().tcdiff_set_scores(_p(ref_mu), _p(ref_cov), _p(mu), _p(cov), _p(div_rows), div_rows.numel(), mu.numel(),
+                                       max_sweeps, _p(fid), _p(div), _p(status), stream()), "tcdiff_set_scores")
+
+
+def set_check(status):
+    """waits for the stream; raises if the eigen-solver of the tcdiff_set_scores call that wrote ``status`` hit its sweep cap"""
+    L.check(L.load().tcdiff_set_check(_p(status), stream()), "tcdiff_set_check")
+
+
 # ---- stick-figure frames ---------------------------------------------------------------------------------------------------
 def draw_project(joints, contacts, view, floor, up, contact_threshold, still, pts, trail, order, planted):
     """joints (b, dn, T, 24, 3) / contacts (b, dn, T, 4) fp32 views, read by their strides; view: 12 floats (row-major 3 x 4)"""
