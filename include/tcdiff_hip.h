@@ -807,6 +807,65 @@ int tcdiff_set_scores(const double* ref_mu, const double* ref_cov, const double*
                       long M, int D, int max_sweeps, double* fid, double* div, int* status, hipStream_t stream);
 int tcdiff_set_check(const int* status, hipStream_t stream);
 
+/* ---- music features: the STFT path (csrc/music.hip) ---------------------------------------------------------------------------
+ * From a waveform to 425 of the 438 columns of `cond`, as the reference computes them on the CPU with librosa 0.9
+ * (data/data_preprocess/dataset_utils.py:45-86), restated here because librosa is not a dependency; parity with librosa's own
+ * output is not pinned.  fp32 arithmetic, B clips per launch, no atomics, every sum in a fixed order: a second run, and a clip
+ * computed alone, give the same bits.  Eleven launches for a whole feature matrix, whatever B.  Fixed: n_fft 2048, hop 512,
+ * periodic Hann windows, 128 mel bands, 20 MFCC, tempogram window 384, HPSS kernel 31, mask power 2, margin 1.
+ * A clip has n >= 2048 samples and T = 1 + n / 512 frames.  FLT_MIN below is the smallest normal float.
+ *
+ * Tables, all DEVICE, computed by the host in float64 and rounded once:
+ *   twiddle   [1024][2] float   (cos, -sin)(2 pi k / 2048)
+ *   window    [2048] float for the STFT launchers, [384] for tcdiff_music_onset:  0.5 - 0.5 cos(2 pi i / N)
+ *   mel_w     [128][1025] float: Slaney mel scale (linear below 1 kHz at 200/3 Hz per mel, logarithmic above with step ln(6.4)/27),
+ *             130 points equally spaced in mel over [0, sr/2], triangular filters between them over the bins k sr / 2048, each
+ *             scaled by 2 / (f[i+2] - f[i]);  mel_range [128][2] int: filter i is zero outside bins [lo, hi)
+ *   dct       [20][128] float: s_k cos(pi (2 m + 1) k / 256), s_0 = sqrt(1/128), s_k = sqrt(2/128)  (orthonormal DCT-II)
+ *
+ * tcdiff_music_stft, one launch.  y: clip b at y + b * y_stride, n floats.
+ *   The clip is padded by 1024 on both sides by reflection (edge sample not repeated); frame t is padded samples
+ *   [512 t, 512 t + 2048) times the window; D[b][t][k], k <= 1024, its DFT (interleaved re, im); S = |D|; M[b][t][i] =
+ *   sum_k mel_w[i][k] S[b][t][k]^2 in ascending k;  frame_max[b][t] = max_i M[b][t][i].  D and S are both given or both NULL
+ *   (the mel power alone).
+ *
+ * tcdiff_music_mfcc, two launches.  M [B][T][128], frame_max [B][T] -> mx [B] = the largest M of each clip (workspace);
+ *   mel_db[b][t][i] = max(-80, 10 log10(max(1e-10, M)) - 10 log10(max(1e-10, mx[b])))  (the largest dB of a clip is 0);
+ *   feats[b][t][k] = sum_i dct[k][i] mel_db[b][t][i], k < 20;  feats[b][t][20 + k] = (x[c + 1] - x[c - 1]) / 2 of column k with
+ *   c = t clamped to [1, T - 2]  (scipy.signal.savgol_filter, window 3, order 1, mode 'interp').  feats rows have TC_MUSIC_COLS floats.
+ *
+ * tcdiff_music_hpss, three launches.  H / P [B][T][1025] = the 31-tap median of S along t / along k, the axis extended as
+ *   scipy.ndimage's 'reflect' (edge sample repeated, period twice the length): an exact selection per element.
+ *   mask(X, R) = 0.5 where Z = max(X, R) < FLT_MIN, else (X/Z)^2 / ((X/Z)^2 + (R/Z)^2).
+ *   frames [B][W][T][2048] (workspace, W = 2, or 1 when harmonic is NULL): the inverse real DFT of D mask(P, H) (part 0) and of
+ *   D mask(H, P) (part 1), divided by 2048, times the window.  percussive / harmonic [B][n]: sample i is padded sample
+ *   p = i + 1024; the sum over the frames t with 512 t <= p < 512 t + 2048 in ascending t of frames[t][p - 512 t], divided by the
+ *   sum of window[p - 512 t]^2 over the same frames where that exceeds FLT_MIN; 0 where there is no frame.
+ *
+ * tcdiff_music_onset, three launches.  M [B][T][128]: the mel power of the PERCUSSIVE signal (tcdiff_music_stft on the whole clip
+ *   percussive[b]) and its frame_max; mx [B] workspace.  dB = max(10 log10(max(1e-10, M)), 10 log10(max(1e-10, mx[b])) - 80).
+ *   onset_env[b][t] = 0 for t < 3, else the median over i of max(0, dB[t - 2][i] - dB[t - 3][i]) (the mean of the two middle
+ *   values); also stored at feats[b][t][40].  Tempogram: onset_env padded by 192 on both sides as numpy.pad's 'linear_ramp' to 0;
+ *   x = padded samples [t, t + 384) times the 384-window; a[l] = sum_i x[i] x[i + l] over i + l < 384 in ascending i;
+ *   feats[b][t][41 + l] = a[l] / max_l |a[l]|, or a[l] where that maximum is below FLT_MIN.
+ *
+ * TC_ERR_ARG for a NULL pointer (those named optional excepted), B < 1, n < 2048 or T < 5; TC_ERR_UNSUPPORTED for B > 65535 or
+ * n > 2^29. */
+#define TC_MUSIC_N_FFT 2048
+#define TC_MUSIC_HOP 512
+#define TC_MUSIC_N_MELS 128
+#define TC_MUSIC_N_MFCC 20
+#define TC_MUSIC_TEMPO_WIN 384
+#define TC_MUSIC_COLS 425            /* mfcc 0-19, delta 20-39, onset_env 40, tempogram 41-424 */
+int tcdiff_music_stft(const float* y, long y_stride, int B, int n, const float* twiddle, const float* window, const float* mel_w,
+                      const int* mel_range, float* D, float* S, float* M, float* frame_max, hipStream_t stream);
+int tcdiff_music_mfcc(const float* M, const float* frame_max, int B, int T, const float* dct, float* mx, float* mel_db, float* feats,
+                      hipStream_t stream);
+int tcdiff_music_hpss(const float* D, const float* S, int B, int n, const float* twiddle, const float* window, float* H, float* P,
+                      float* frames, float* percussive, float* harmonic, hipStream_t stream);
+int tcdiff_music_onset(const float* M, const float* frame_max, int B, int T, const float* window, float* mx, float* onset_env,
+                       float* feats, hipStream_t stream);
+
 /* ---- stick-figure frames (csrc/draw.hip) -----------------------------------------------------------------------------------
  * What skeleton_render (vis.py:223-327) shows of a generated dance -- 23 bones per dancer, the root's trail on the floor and
  * four foot markers -- as RGB frames, in two launches for any number of clips: no host synchronisation, no atomics, a fixed

@@ -7,7 +7,8 @@ trains on, in two launches for any number of clips (``tcdiff_motion_ingest``, cs
 * ``AIOZDataset`` has the reference's constructor, attributes and items; its file logic (``load_aioz``, :99-165) runs on the
   host.
 The reference goes through pytorch3d (absent here: arithmetic restated from its published definitions -- "parity unpinned").
-The music features (``feats438``) are read from disk as the reference reads them; computing them is not part of this.
+The music features (``feats438``) are read from disk as the reference reads them; ``tcdiff_amd.music`` computes 425 of their 438
+columns from a waveform on the GPU (the chroma and the beat track are the caller's), and ``assemble_cond`` lays the row out.
 """
 from __future__ import annotations
 

@@ -591,6 +591,35 @@ def set_check(status):
     L.check(L.load().tcdiff_set_check(_p(status), stream()), "tcdiff_set_check")
 
 
+# ---- music features: the STFT path -------------------------------------------------------------------------------------------
+def music_stft(y, tab, D, S, M, frame_max):
+    """y (B, n) fp32 view read through its row stride; tab: music._tables; D (B, T, 1025, 2) and S (B, T, 1025), both or neither;
+    M (B, T, 128) and its maximum per frame, frame_max (B, T)"""
+    B, n = y.shape
+    L.check(L.load().tcdiff_music_stft(_p(y), y.stride(0) if B > 1 else n, B, n, _p(tab["twiddle"]), _p(tab["window"]), _p(tab["mel_w"]),
+                                       _p(tab["mel_range"]), _p(D), _p(S), _p(M), _p(frame_max), stream()), "tcdiff_music_stft")
+
+
+def music_mfcc(M, frame_max, tab, mx, mel_db, feats):
+    """M (B, T, 128), frame_max (B, T) of music_stft -> mx (B,) workspace, mel_db (B, T, 128), columns 0-39 of feats (B, T, 425)"""
+    B, T = M.shape[:2]
+    L.check(L.load().tcdiff_music_mfcc(_p(M), _p(frame_max), B, T, _p(tab["dct"]), _p(mx), _p(mel_db), _p(feats), stream()), "tcdiff_music_mfcc")
+
+
+def music_hpss(D, S, n, tab, H, P, frames, percussive, harmonic):
+    """D, S of music_stft -> H, P (B, T, 1025) and frames (B, W, T, 2048) workspaces; percussive and (or None) harmonic (B, n)"""
+    B = S.shape[0]
+    L.check(L.load().tcdiff_music_hpss(_p(D), _p(S), B, n, _p(tab["twiddle"]), _p(tab["window"]), _p(H), _p(P), _p(frames),
+                                       _p(percussive), _p(harmonic), stream()), "tcdiff_music_hpss")
+
+
+def music_onset(M, frame_max, tab, mx, onset_env, feats):
+    """M (B, T, 128), frame_max (B, T): music_stft of the percussive signal -> mx (B,) workspace, onset_env (B, T), columns 40-424 of feats"""
+    B, T = M.shape[:2]
+    L.check(L.load().tcdiff_music_onset(_p(M), _p(frame_max), B, T, _p(tab["tempo_window"]), _p(mx), _p(onset_env), _p(feats), stream()),
+            "tcdiff_music_onset")
+
+
 # ---- stick-figure frames ---------------------------------------------------------------------------------------------------
 def draw_project(joints, contacts, view, floor, up, contact_threshold, still, pts, trail, order, planted):
     """joints (b, dn, T, 24, 3) / contacts (b, dn, T, 4) fp32 views, read by their strides; view: 12 floats (row-major 3 x 4)"""
