@@ -866,6 +866,64 @@ int tcdiff_music_hpss(const float* D, const float* S, int B, int n, const float*
 int tcdiff_music_onset(const float* M, const float* frame_max, int B, int T, const float* window, float* mx, float* onset_env,
                        float* feats, hipStream_t stream);
 
+/* ---- music features: the beat track (csrc/beat.hip) --------------------------------------------------------------------------
+ * Column 53 of `cond`, onset_beat: the one-hot output of librosa's beat tracker run on the onset envelope
+ * (data/data_preprocess/_preprocess_wav.py:70-83; dataset_utils.py:72 keeps element [0] of the pair, so peak_pick is not built).
+ * librosa 0.9.2's beat.beat_track, beat.tempo and beat.__beat_tracker restated for one float envelope o[0 .. T) per clip, T >= 5,
+ * at 60 frames / s (the only rate supported); parity with librosa's own output is not pinned.  Precondition: every envelope
+ * value is finite and >= 0, as music_features' onset_env is (a negative or NaN value gives NaN scores, which the kernel's
+ * maxima skip where numpy's argmax would return the first NaN: the result is then unspecified).  Two launches for any number of
+ * clips (tcdiff_beat_tempo, tcdiff_beat_track), one when the period is given; no float atomics, every sum in a fixed order: a
+ * second run, and a clip computed alone, give the same bits.  Three quirks of 0.9.2 are kept on purpose: (1) np.round rounds
+ * half to even (period = round(3600 / bpm) on the host, h below); (2) the end of the trim slice is exclusive; (3) the trim's
+ * symmetric 5-point Hann window has zero end taps.
+ *
+ * Tables, DEVICE, computed by the host in float64 (nothing is computed in-kernel):
+ *   window  [480] float   0.5 - 0.5 cos(2 pi i / 480)
+ *   prior   [480] double  -0.5 ((log2(3600 / l) - log2(start_bpm)) / std_bpm)^2;  -inf for l = 0 and wherever 3600 / l >= max_tempo
+ *   tables  [2][TC_BEAT_TABLE] double, one row per period p = 1 .. 479 in each half, row p at offset p^2 - 1:
+ *           half 0  w[j + p]  = exp(-0.5 (32 j / p)^2), j = -p .. p                          (2 p + 1 values)
+ *           half 1  txwt[k]   = -tightness ln(-d_k / p)^2, d_k = -2 p + k, k = 0 .. 2 p - h  (2 p - h + 1 values),
+ *                   h = rint(p / 2), half to even
+ *
+ * tcdiff_beat_tempo, one launch.  onset_env: clip b at onset_env + b * o_stride, T floats.  The envelope is padded by 240 on
+ *   both sides as numpy.pad's 'linear_ramp' to 0; for each frame t, x = padded samples [t, t + 480) times the window;
+ *   a_t[l] = sum_i x[i] x[i + l] over i + l < 480 in ascending i, in fp32 (the tempogram's form and device code), divided by
+ *   max_l |a_t[l]| unless that is below FLT_MIN.  partial[b][c][l], c < ceil(T / TC_BEAT_CHUNK) = the float64 sum of the
+ *   normalised a_t[l] over the frames t of chunk c in ascending t.
+ *
+ * tcdiff_beat_track, one launch, one workgroup per clip.  Float64 from here on.
+ *   Period.  partial given (period_host NULL): g[l] = (sum_c partial[b][c][l] in ascending c) / T;
+ *     score[l] = log1p(1e6 g[l]) + prior[l];  lag = the first argmax;  period[b] = lag, tempo[b] = 3600 / lag.
+ *     partial NULL: the caller has put the periods, ints in [1, 479], into period [B] (DEVICE) and the same values into
+ *     period_host [B] (HOST, only read by the launcher's range check); tempo is the caller's (only a silent clip's is set).
+ *   A clip whose envelope is all zero gets tempo 0 and no beats; one whose samples are all equal (zero variance) no beats: their
+ *     local_score and cum_score rows are 0, their backlink rows -1.
+ *   Local score.  x = o / std(o, ddof = 1).  Both sums of the standard deviation (of o, then of (o - mean)^2 with mean = sum / T;
+ *     var = sum / (T - 1)) run in this order: partial p < 512 adds its elements p, p + 512, p + 1024, ... in ascending order
+ *     (fused multiply-adds allowed), then s[p] += s[p + k] for p < k, k = 256, 128, ... 1; s[0] is the sum.
+ *     ls[i] = sum_j w[j] x[i - j], j = -p .. p ascending, x zero outside the clip; each term a rounded product, then a rounded add.
+ *   Dynamic programme, i ascending: c[k] = txwt[k] + (cum[i + d_k] if i + d_k >= 0 else 0); k* = the first argmax;
+ *     cum[i] = ls[i] + c[k*];  backlink[i] = -1 for i < f, else i + d_k*, f = the first i with ls[i] >= 0.01 max(ls).
+ *     Frames i .. i + h - 1 never read one another's cum: the kernel runs blocks of h frames between barriers.
+ *   Last beat.  m[i] = cum[i] > cum[i - 1] and cum[i] >= cum[i + 1], the ends repeating their edge value (m[0] is false);
+ *     med = the exact median of cum[m] (the mean of the two middle values for an even count);
+ *     last = the largest i with m[i] and 2 cum[i] > med.  No flagged frame, or none above the median: no beats.
+ *   Backtrace and trim.  beats[0 .. n) = last, backlink[last], ... while >= 0, reversed (beats_ws: workspace, in backtrace order);
+ *     s[q] = 0.5 ls[beats[q - 1]] + ls[beats[q]] + 0.5 ls[beats[q + 1]], terms outside the array dropped;
+ *     thr = 0.5 sqrt(mean(s^2)) if trim else 0;  v0 / v1 = the first / last q with s[q] > thr;  kept: beats[v0 : v1].
+ *     onset_beat[b][t] = 1.0f at the kept beats, 0 elsewhere;  n_beats[b] = their number.
+ *
+ * TC_ERR_ARG for a NULL pointer (those named optional excepted; exactly one of partial and period_host is given, prior with
+ * partial), B < 1, T < 5 or a period outside [1, 479]; TC_ERR_UNSUPPORTED for B > 65535 or T > 2^20. */
+#define TC_BEAT_WIN 480
+#define TC_BEAT_CHUNK 8              /* frames per workgroup of tcdiff_beat_tempo */
+#define TC_BEAT_TABLE (480 * 480 - 1)
+int tcdiff_beat_tempo(const float* onset_env, long o_stride, int B, int T, const float* window, double* partial, hipStream_t stream);
+int tcdiff_beat_track(const float* onset_env, long o_stride, int B, int T, const double* partial, const double* prior,
+                      const double* tables, const int* period_host, int trim, double* local_score, double* cum_score, int* backlink,
+                      int* beats_ws, float* onset_beat, int* period, int* n_beats, double* tempo, hipStream_t stream);
+
 /* ---- stick-figure frames (csrc/draw.hip) -----------------------------------------------------------------------------------
  * What skeleton_render (vis.py:223-327) shows of a generated dance -- 23 bones per dancer, the root's trail on the floor and
  * four foot markers -- as RGB frames, in two launches for any number of clips: no host synchronisation, no atomics, a fixed

@@ -16,6 +16,7 @@
 #include <float.h>
 
 #include "common.h"
+#include "music_acf.h"
 #include "tcdiff_hip.h"
 
 #define MU_NFFT TC_MUSIC_N_FFT
@@ -315,27 +316,12 @@ __global__ __launch_bounds__(MU_TEMPO / 2) void music_tempogram_kernel(const flo
     const int tid = threadIdx.x, t = blockIdx.x;
     const long b = blockIdx.y;
     const float* env = onset_env + b * T;
-    for (int i = tid; i < MU_TEMPO; i += MU_TEMPO / 2) {
-        const int j = t + i - MU_TEMPO / 2;
-        float x;
-        if (j < 0) x = (float)(t + i) * (env[0] / (float)(MU_TEMPO / 2));
-        else if (j >= T) x = (float)(MU_TEMPO / 2 - 1 - (j - T)) * (env[T - 1] / (float)(MU_TEMPO / 2));
-        else x = env[j];
-        s_x[i] = x * win[i];
-    }
+    for (int i = tid; i < MU_TEMPO; i += MU_TEMPO / 2) s_x[i] = mu_ramp_sample<MU_TEMPO>(env, T, t, i) * win[i];
     __syncthreads();
     const int la = tid, lb = MU_TEMPO - 1 - tid;
-    float a = 0.0f, c = 0.0f;
-    for (int i = 0; i + la < MU_TEMPO; ++i) a += s_x[i] * s_x[i + la];
-    for (int i = 0; i + lb < MU_TEMPO; ++i) c += s_x[i] * s_x[i + lb];
-    s_red[tid] = fmaxf(fabsf(a), fabsf(c));
-    if (tid < 256 - MU_TEMPO / 2) s_red[MU_TEMPO / 2 + tid] = 0.0f;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) s_red[tid] = fmaxf(s_red[tid], s_red[tid + o]);
-        __syncthreads();
-    }
-    const float mx = s_red[0];
+    float a, c;
+    mu_acf_pair<MU_TEMPO>(s_x, tid, a, c);
+    const float mx = mu_acf_absmax<MU_TEMPO>(s_red, a, c, tid);
     float* o = feats + (b * T + t) * MU_COLS + 2 * MU_MFCC + 1;
     o[la] = mx < FLT_MIN ? a : a / mx;
     o[lb] = mx < FLT_MIN ? c : c / mx;

@@ -620,6 +620,25 @@ def music_onset(M, frame_max, tab, mx, onset_env, feats):
             "tcdiff_music_onset")
 
 
+# ---- music features: the beat track -------------------------------------------------------------------------------------------
+def beat_tempo(o, window, partial):
+    """o (B, T) fp32 view read through its row stride; window (480,) fp32 -> partial (B, ceil(T / 8), 480) float64.  One launch."""
+    B, T = o.shape
+    L.check(L.load().tcdiff_beat_tempo(_p(o), o.stride(0) if B > 1 else T, B, T, _p(window), _p(partial), stream()), "tcdiff_beat_tempo")
+
+
+def beat_track(o, partial, prior, tables, period_host, trim, local_score, cum_score, backlink, beats_ws, onset_beat, period, n_beats, tempo):
+    """o (B, T) fp32 view; either partial of beat_tempo with prior (480,) float64, or period_host: the B ints the caller has put
+    into period (the launcher checks their range on the host); tables: music._beat_tables -> local_score, cum_score (B, T) float64, backlink (B, T) int32, beats_ws (B, T) int32
+    workspace, onset_beat (B, T) fp32, period, n_beats (B,) int32, tempo (B,) float64 (the caller's when the period is given).
+    One launch."""
+    B, T = o.shape
+    ph = None if period_host is None else (C.c_int * B)(*[int(p) for p in period_host])
+    L.check(L.load().tcdiff_beat_track(_p(o), o.stride(0) if B > 1 else T, B, T, _p(partial), _p(prior), _p(tables), ph, int(bool(trim)),
+                                       _p(local_score), _p(cum_score), _p(backlink), _p(beats_ws), _p(onset_beat), _p(period), _p(n_beats),
+                                       _p(tempo), stream()), "tcdiff_beat_track")
+
+
 # ---- stick-figure frames ---------------------------------------------------------------------------------------------------
 def draw_project(joints, contacts, view, floor, up, contact_threshold, still, pts, trail, order, planted):
     """joints (b, dn, T, 24, 3) / contacts (b, dn, T, 4) fp32 views, read by their strides; view: 12 floats (row-major 3 x 4)"""

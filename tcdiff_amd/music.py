@@ -4,9 +4,13 @@ hangs off one STFT, on the device (csrc/music.hip, the definitions in include/tc
     feats = music_features(audio)                          # (B, T, 425): mfcc, delta, onset_env, tempogram
     cond = assemble_cond(feats, chroma, onset_beat)        # (B, T, 438), the layout every entry point of this package reads
 
-The caller brings samples at ``sr`` (decoding and resampling audio files is not part of this) and the two parts this does not
-compute: ``chroma`` (librosa's chroma_cqt of the harmonic signal, columns 40-51) and ``onset_beat`` (its beat tracker run on the
-onset envelope, column 53).  ``return_parts=True`` hands out their inputs, ``harmonic`` and ``onset_env``.
+The caller brings samples at ``sr`` (decoding and resampling audio files is not part of this) and the two parts
+``music_features`` does not compute: ``chroma`` (librosa's chroma_cqt of the harmonic signal, columns 40-51) and ``onset_beat``
+(its beat tracker run on the onset envelope, column 53).  ``return_parts=True`` hands out their inputs, ``harmonic`` and
+``onset_env``.  The second of the two is built as well (csrc/beat.hip):
+
+    tempo, onset_beat = beat_track(parts["onset_env"])     # (B,) float64 beats per minute, (B, T) one-hot: two more launches
+    cond = music_cond(audio, chroma)                       # the three calls chained
 
 Eleven launches for any number of clips: STFT + mel power; clip maximum; dB + MFCC + delta; the two 31-tap medians; masks + inverse
 FFT; overlap-add; STFT + mel power of the percussive signal; its clip maximum; onset envelope; tempogram.  The definitions restate
@@ -22,6 +26,7 @@ from . import kernels as K
 N_FFT, HOP, N_BINS, N_MELS, N_MFCC, TEMPO_WIN, N_COLS = L.MUSIC_N_FFT, L.MUSIC_HOP, L.MUSIC_N_FFT // 2 + 1, L.MUSIC_N_MELS, \
     L.MUSIC_N_MFCC, L.MUSIC_TEMPO_WIN, L.MUSIC_COLS
 COND_COLS, CHROMA0, N_CHROMA, ONSET_BEAT = 438, 40, 12, 53      # the row of dataset_utils.py:75-82 (metrics.ONSET_BEAT)
+BEAT_WIN = L.BEAT_WIN                                     # the tempo estimate's 8-second window; beat periods are 1 .. 479 frames
 
 _TABLES = {}
 
@@ -114,6 +119,125 @@ def music_features(audio, *, sr=30720, return_parts=False):
     if return_parts:
         return feats, dict(mel_db=mel_db, harmonic=harmonic, percussive=percussive, onset_env=onset_env)
     return feats
+
+
+def beat_tables(tightness) -> np.ndarray:
+    """(2, 480^2 - 1) float64, the tracker's two tables for every period p = 1 .. 479, row p at offset p^2 - 1 (include/tcdiff_hip.h):
+    the local score's window exp(-0.5 (32 j / p)^2), j = -p .. p, and the programme's transition score
+    -tightness ln(-d / p)^2, d = -2 p .. -rint(p / 2) (numpy's round: half to even)"""
+    tab = np.zeros((2, L.BEAT_TABLE), np.float64)
+    with np.errstate(divide="ignore"):                    # p = 1: d = 0 scores -inf
+        for p in range(1, BEAT_WIN):
+            at = p * p - 1
+            tab[0, at:at + 2 * p + 1] = np.exp(-0.5 * (np.arange(-p, p + 1) * 32.0 / p) ** 2)
+            d = np.arange(-2 * p, -int(np.round(p / 2)) + 1)
+            tab[1, at:at + len(d)] = -tightness * (np.log(-d / p) ** 2)
+    return tab
+
+
+def tempo_prior(start_bpm, std_bpm, max_tempo) -> np.ndarray:
+    """(480,) float64: the log-normal prior over the lags' tempi 3600 / l; -inf for l = 0 and wherever 3600 / l >= max_tempo"""
+    with np.errstate(divide="ignore"):
+        bpms = 3600.0 / np.arange(BEAT_WIN)
+    prior = -0.5 * ((np.log2(bpms) - np.log2(start_bpm)) / std_bpm) ** 2
+    prior[bpms >= max_tempo] = -np.inf
+    return prior
+
+
+def _beat_tables(tightness, device):
+    """uploaded once per (tightness, device), as ``_tables``"""
+    key = ("beat", float(tightness), str(device))
+    tab = _TABLES.get(key)
+    if tab is None:
+        tab = dict(tables=torch.from_numpy(beat_tables(float(tightness))).to(device),
+                   window=torch.from_numpy(_hann(BEAT_WIN).astype(np.float32)).to(device))
+        _TABLES[key] = tab
+    return tab
+
+
+def _beat_prior(start_bpm, std_bpm, max_tempo, device):
+    key = ("prior", start_bpm, std_bpm, max_tempo, str(device))
+    tab = _TABLES.get(key)
+    if tab is None:
+        tab = _TABLES[key] = torch.from_numpy(tempo_prior(start_bpm, std_bpm, max_tempo)).to(device)
+    return tab
+
+
+def _positive(name, v):
+    try:
+        v = float(v)
+    except (TypeError, ValueError):
+        raise L.TcdiffError(f"beat_track: {name} must be a number, got {v!r}") from None
+    if not (v > 0 and np.isfinite(v)):
+        raise L.TcdiffError(f"beat_track: {name} must be positive and finite, got {v!r}")
+    return v
+
+
+def beat_track(onset_env, *, bpm=None, start_bpm=120.0, std_bpm=1.0, max_tempo=320.0, tightness=100.0, trim=True, return_parts=False):
+    """onset_env (T,) or (B, T) float32 on the device, T >= 5 frames at 60 per second (``parts["onset_env"]`` of
+    ``music_features``; finite and non-negative), read through its row stride -> (tempo (B,) float64 in beats per minute, onset_beat (B, T) float32, 1 at
+    the beat frames): librosa 0.9.2's ``beat.beat_track`` -- tempo from the mean 8-second autocorrelation under a log-normal
+    prior, then the dynamic-programme tracker, with librosa's trimming of weak leading / trailing beats -- in two launches, or one
+    when ``bpm`` (a number, or one per clip) is given.  A silent clip has tempo 0 and no beats.
+
+    ``return_parts=True`` -> (tempo, onset_beat, parts): ``period`` (B,) int32 frames per beat, ``local_score`` and ``cum_score``
+    (B, T) float64, ``backlink`` (B, T) int32, ``n_beats`` (B,) int32."""
+    if not isinstance(onset_env, torch.Tensor) or onset_env.dim() not in (1, 2):
+        raise L.TcdiffError(f"beat_track: onset_env must be (T,) or (B, T), got "
+                            f"{tuple(onset_env.shape) if isinstance(onset_env, torch.Tensor) else type(onset_env)}")
+    if onset_env.dtype != torch.float32:
+        raise L.TcdiffError(f"beat_track: onset_env must be float32, got {onset_env.dtype}")
+    o = onset_env if onset_env.dim() == 2 else onset_env[None]
+    B, T = o.shape
+    if B < 1:
+        raise L.TcdiffError("beat_track: onset_env has no clip")
+    if T < 5:
+        raise L.TcdiffError(f"beat_track: a clip needs at least 5 frames, got {T}")
+    if o.stride(1) != 1:
+        raise L.TcdiffError(f"beat_track: the last dimension of onset_env must be contiguous (strides {tuple(onset_env.stride())})")
+    tightness = _positive("tightness", tightness)
+    periods = None
+    if bpm is None:
+        start_bpm, std_bpm, max_tempo = _positive("start_bpm", start_bpm), _positive("std_bpm", std_bpm), _positive("max_tempo", max_tempo)
+        if not max_tempo > 3600.0 / (BEAT_WIN - 1):
+            raise L.TcdiffError(f"beat_track: max_tempo {max_tempo} leaves no lag below {BEAT_WIN}")
+    else:
+        bpms = [bpm] * B if np.ndim(bpm) == 0 else list(bpm)
+        if len(bpms) != B:
+            raise L.TcdiffError(f"beat_track: bpm must be a number or one per clip ({B}), got {len(bpms)}")
+        bpms = [_positive("bpm", v) for v in bpms]
+        periods = [int(np.round(3600.0 / v)) for v in bpms]           # half to even, as librosa 0.9.2
+        if not all(1 <= p < BEAT_WIN for p in periods):
+            raise L.TcdiffError(f"beat_track: bpm {bpm!r} gives a period outside [1, {BEAT_WIN - 1}] frames")
+    if not o.is_cuda:
+        raise L.TcdiffError("beat_track runs on MI355X only (no CPU fallback)")
+    dev = o.device
+    new = lambda dt, *s: torch.empty(*s, dtype=dt, device=dev)
+    with torch.cuda.device(dev):
+        tab = _beat_tables(tightness, dev)
+        local_score, cum_score = new(torch.float64, B, T), new(torch.float64, B, T)
+        backlink, beats_ws, onset_beat = new(torch.int32, B, T), new(torch.int32, B, T), new(torch.float32, B, T)
+        n_beats = new(torch.int32, B)
+        if periods is None:
+            tempo, period, prior = new(torch.float64, B), new(torch.int32, B), _beat_prior(start_bpm, std_bpm, max_tempo, dev)
+            partial = new(torch.float64, B, -(-T // L.BEAT_CHUNK), BEAT_WIN)
+            K.beat_tempo(o, tab["window"], partial)
+        else:
+            tempo, period = torch.tensor(bpms, dtype=torch.float64, device=dev), torch.tensor(periods, dtype=torch.int32, device=dev)
+            prior = partial = None
+        K.beat_track(o, partial, prior, tab["tables"], periods, trim, local_score, cum_score, backlink, beats_ws, onset_beat, period,
+                     n_beats, tempo)
+    if return_parts:
+        return tempo, onset_beat, dict(period=period, local_score=local_score, cum_score=cum_score, backlink=backlink, n_beats=n_beats)
+    return tempo, onset_beat
+
+
+def music_cond(audio, chroma, *, sr=30720) -> torch.Tensor:
+    """audio (n,) or (B, n) float32 on the device, chroma (B, T, 12) -> cond (B, T, 438): ``music_features``, ``beat_track`` of its
+    onset envelope and ``assemble_cond``.  ``chroma`` (columns 40-51) stays the caller's."""
+    feats, parts = music_features(audio, sr=sr, return_parts=True)
+    _, onset_beat = beat_track(parts["onset_env"])
+    return assemble_cond(feats, chroma, onset_beat)
 
 
 def assemble_cond(stft_feats, chroma, onset_beat) -> torch.Tensor:
