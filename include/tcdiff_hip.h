@@ -924,6 +924,84 @@ int tcdiff_beat_track(const float* onset_env, long o_stride, int B, int T, const
                       const double* tables, const int* period_host, int trim, double* local_score, double* cum_score, int* backlink,
                       int* beats_ws, float* onset_beat, int* period, int* n_beats, double* tempo, hipStream_t stream);
 
+/* ---- music features: the chroma columns (csrc/chroma.hip) -----------------------------------------------------------------------
+ * Columns 40-51 of `cond`: librosa.feature.chroma_cqt(y=audio_harmonic, sr=30720, n_octaves=7) of
+ * data/data_preprocess/_preprocess_wav.py:45-47 and dataset_utils.py:69, that is librosa 0.9.2's estimate_tuning (piptrack +
+ * pitch_tuning), its seven-octave constant-Q transform (36 bins per octave from C1, hop 512) with resampy's kaiser_fast decimation
+ * by two between octaves, and the fold to 12 chroma.  Everything below restates librosa 0.9.2 and resampy at those arguments FROM
+ * KNOWLEDGE OF THOSE VERSIONS, NOT FROM THEIR SOURCE, which is not available where this is built; like the rest of the music path,
+ * parity with librosa's own output is not pinned.  The one default this restatement is least sure of is the constant-Q frames'
+ * padding (zeros, librosa 0.9's pad_mode='constant' for cqt; see the response).  fp32 arithmetic unless said otherwise, B clips
+ * per launch, no float atomics, every sum in a fixed order: a second run, and a clip computed alone, give the same bits.  Four
+ * launches for any number of clips (one of them tcdiff_music_stft on the harmonic signal), two when the tuning is given.  A clip
+ * has n >= 2048 samples and T = 1 + n / 512 frames.  FLT_MIN is the smallest normal float.
+ *
+ * Constants: bins_per_octave 36, n_octaves 7, n_bins 252, fmin0 = 32.70319566257483 Hz (C1), alpha = 2^(1/36) - 1, Q = 1 / alpha,
+ * Hann window_bandwidth 1.50018310546875, BW_FASTEST 0.85.  A tuning is one of the 100 values
+ * EDGES[k] = linspace(-0.5, 0.5, 101)[k], k = 0 .. 99, in fractions of a 1/36-octave bin.
+ *
+ * Tables, all DEVICE, computed by the host in float64 and rounded once:
+ *   taps     [63] float: h[j + 31] = 0.5 win[256 |j|], j = -31 .. 31, of the kaiser_fast table
+ *            win[m] = 0.85 sinc(0.85 m / 512) kaiser(2 * 8192 + 1, beta = 8.555504641634386)[8192 + m], m = 0 .. 8192 (sinc(x) =
+ *            sin(pi x) / (pi x); m = 8192 is never reached): resampy's interpolating resampler at ratio 1/2 reads only these entries.
+ *   twiddle  [512][2] float  (cos, -sin)(2 pi k / 1024)
+ *   edges    [101] double    EDGES
+ *   basis    [100][36][TC_CHROMA_BAND][2] float, band [100][36][2] int, per tuning k, for the top octave's frequencies
+ *            f_r = fmin0 2^(EDGES[k] / 36) 2^(6 + r / 36), r < 36:  len = Q sr / f_r;  the time filter exp(2 pi i f_r a / sr)
+ *            over a = arange(-len // 2, len // 2) (floats: floor(len) or ceil(len) points) times the periodic Hann window of
+ *            floor(len) points, zero-extended where the filter is one point longer; divided by its L1 norm; centre-padded to
+ *            1024 ((1024 - points) // 2 zeros in front); times len / 1024; its 1024-point DFT, bins 0 .. 512; per row, entries
+ *            below the magnitude at the first index where the ascending cumulative magnitude reaches 1 % of the row's sum are
+ *            set to zero; rounded to complex64.  Row r keeps bins [lo, hi) = band[k][r] (its first to last nonzero, zeros
+ *            inside kept, hi - lo <= TC_CHROMA_BAND) at basis[k][r][0 .. hi - lo).  f / sr is the same in every octave up to
+ *            exact powers of two, so octave i uses this basis times sqrt(2^i).
+ *   scale    [100][252] float, lowest bin first: sqrt(2^i) / sqrt(Q sr / f_bin), i = 6 - bin / 36,
+ *            f_bin = fmin0 2^(EDGES[k] / 36) 2^(bin / 36)
+ *   At these settings librosa does no early downsampling and handles no top octave apart (the top filter's cutoff, about 4.17 kHz,
+ *   is below 0.85 Nyquist, and the downsample count is 0 for every tuning in [-0.5, 0.5)); the host asserts both.
+ *
+ * tcdiff_chroma_pyramid, one launch.  y: clip b at y + b * y_stride, n floats.  pyramid [B][P], P = sum_{s = 1 .. 6} ceil(n / 2^s):
+ *   signals 1 .. 6 one after another, signal s (ceil(n / 2^s) samples) = y_s[t] = sqrt(2) sum_j h[j] y_{s-1}[2 t + j], j = -31 .. 31
+ *   ascending (fused multiply-adds), terms outside the signal dropped, t = 0 .. ceil(len / 2) - 1; y_0 = y.  (librosa zero-fills the
+ *   last sample of an odd-length signal's half instead of computing it.)
+ *
+ * tcdiff_chroma_tuning, one launch, one workgroup per clip.  S [B][T][1025]: |STFT| of the clip, n_fft 2048, hop 512, periodic
+ *   Hann, centred, reflect padding (S of tcdiff_music_stft).  For bins f_lo <= f <= f_hi (the host's: 150 <= f sr / 2048 < 4000;
+ *   1 <= f_lo, f_hi <= 1023):  avg = 0.5 (S[f+1] - S[f-1]);  den = 2 S[f] - S[f+1] - S[f-1];  shift = avg / (den + (|den| < FLT_MIN));
+ *   dskew = 0.5 avg shift;  with M = S where S > 0.1 max_f S[t][:] (all 1025 bins) else 0, bin f is a pitch when M[f] > M[f-1]
+ *   and M[f] >= M[f+1];  pitch = (f + shift) bin_hz (bin_hz = sr / 2048; float32), mag = S[f] + dskew.  Per clip: thr = the
+ *   exact median of mag over the pitches (the mean of the two middle values for an even count, in float32); for the pitches with
+ *   mag >= thr, in float64 from the float32 pitch (librosa: float32), r = mod(36 log2(pitch / 27.5), 1), less 1 where r >= 0.5;
+ *   counts[b][k] = the number of r in [edges[k], edges[k+1]) (numpy.histogram);  tuning_index[b] = the first argmax;
+ *   n_pitches[b], threshold[b] as named.  A clip with no pitch: index 50 (tuning 0.0), threshold 0, counts 0.
+ *   pitch_ws / mag_ws [B][T][f_hi - f_lo + 1] workspaces (the clip's pitches, packed in no particular order: every step after
+ *   piptrack counts, so the result does not depend on it).
+ *
+ * tcdiff_chroma_response, one launch, one workgroup per (clip, frame).  Octave i = 0 (the top 36 bins) .. 6 (the bottom 36) reads
+ *   y_i at hop 512 / 2^i: frame t holds the 1024 samples centred on t 512 / 2^i, ZEROS outside the signal (see above), rectangular
+ *   window; X = its 1024-point DFT;  C[r] = sum_f basis[k][r][f] X[f] over the row's band in ascending f, k = tuning_index[b]
+ *   (DEVICE; clamped to 0 .. 99);  cqt_mag[b][t][36 (6 - i) + r] = |C[r]| scale[k][36 (6 - i) + r] (optional output);
+ *   raw[c] = sum over the octaves, lowest first, of cqt_mag at bins 3 c - 1, 3 c, 3 c + 1 (mod 36) of the octave;
+ *   chroma[b][t][c] = raw[c] / max_c raw, or raw[c] where that maximum is below FLT_MIN.  Every octave has at least T frames
+ *   (they disagree when n = 512 k - 1): T is their minimum.
+ *
+ * TC_ERR_ARG for a NULL pointer (cqt_mag excepted), B < 1, n < 2048, T < 5 or bins outside [1, 1023]; TC_ERR_UNSUPPORTED for
+ * B > 65535, n >= 2^29 or T > 2^20. */
+#define TC_CHROMA_BPO 36
+#define TC_CHROMA_OCTAVES 7
+#define TC_CHROMA_BINS 252
+#define TC_CHROMA_N 12
+#define TC_CHROMA_N_FFT 1024
+#define TC_CHROMA_BAND 24            /* the widest band of any row at sr 30720 is 20 bins */
+#define TC_CHROMA_TUNINGS 100
+#define TC_CHROMA_TAPS 63
+int tcdiff_chroma_pyramid(const float* y, long y_stride, int B, int n, const float* taps, float* pyramid, hipStream_t stream);
+int tcdiff_chroma_tuning(const float* S, int B, int T, int f_lo, int f_hi, float bin_hz, const double* edges, float* pitch_ws,
+                         float* mag_ws, int* tuning_index, int* n_pitches, float* threshold, int* counts, hipStream_t stream);
+int tcdiff_chroma_response(const float* y, long y_stride, const float* pyramid, int B, int n, const int* tuning_index,
+                           const float* twiddle, const float* basis, const int* band, const float* scale, float* chroma, float* cqt_mag,
+                           hipStream_t stream);
+
 /* ---- stick-figure frames (csrc/draw.hip) -----------------------------------------------------------------------------------
  * What skeleton_render (vis.py:223-327) shows of a generated dance -- 23 bones per dancer, the root's trail on the floor and
  * four foot markers -- as RGB frames, in two launches for any number of clips: no host synchronisation, no atomics, a fixed

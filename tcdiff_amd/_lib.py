@@ -134,6 +134,7 @@ METRICS_WS_PLANES, METRICS_IWS_PLANES, METRICS_MAX_RADIUS = 11, 3, 512      # TC
 SET_MAX_D, SET_MAX_SWEEPS = 72, 30      # TC_SET_*
 MUSIC_N_FFT, MUSIC_HOP, MUSIC_N_MELS, MUSIC_N_MFCC, MUSIC_TEMPO_WIN, MUSIC_COLS = 2048, 512, 128, 20, 384, 425      # TC_MUSIC_*
 BEAT_WIN, BEAT_CHUNK, BEAT_TABLE = 480, 8, 480 * 480 - 1      # TC_BEAT_*
+CHROMA_BPO, CHROMA_OCTAVES, CHROMA_BINS, CHROMA_N, CHROMA_N_FFT, CHROMA_BAND, CHROMA_TUNINGS, CHROMA_TAPS = 36, 7, 252, 12, 1024, 24, 100, 63      # TC_CHROMA_*
 
 _SIGS = {
     "tcdiff_gemm_tile": [_i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, C.POINTER(TileEpi), _vp],
@@ -207,6 +208,10 @@ _SIGS = {
     # music features, the beat track (csrc/beat.hip)
     "tcdiff_beat_tempo": [_vp, _l, _i, _i, _vp, _vp, _vp],
     "tcdiff_beat_track": [_vp, _l, _i, _i, _vp, _vp, _vp, C.POINTER(_i), _i] + [_vp] * 9,
+    # music features, the chroma columns (csrc/chroma.hip)
+    "tcdiff_chroma_pyramid": [_vp, _l, _i, _i, _vp, _vp, _vp],
+    "tcdiff_chroma_tuning": [_vp, _i, _i, _i, _i, _f] + [_vp] * 8,
+    "tcdiff_chroma_response": [_vp, _l, _vp, _i, _i] + [_vp] * 8,
     # stick-figure frames (csrc/draw.hip)
     "tcdiff_draw_project": [_vp, C.POINTER(_l), _vp, C.POINTER(_l), _i, _i, _i, C.POINTER(_f), _f, _i, C.c_double, C.c_double, _vp, _vp,
                             _vp, _vp, _vp],

@@ -639,6 +639,31 @@ def beat_track(o, partial, prior, tables, period_host, trim, local_score, cum_sc
                                        _p(tempo), stream()), "tcdiff_beat_track")
 
 
+# ---- music features: the chroma columns --------------------------------------------------------------------------------------
+def chroma_pyramid(y, taps, pyramid):
+    """y (B, n) fp32 view read through its row stride; taps (63,) fp32 -> pyramid (B, sum_s ceil(n / 2^s)), the six decimated
+    signals one after another.  One launch."""
+    B, n = y.shape
+    L.check(L.load().tcdiff_chroma_pyramid(_p(y), y.stride(0) if B > 1 else n, B, n, _p(taps), _p(pyramid), stream()), "tcdiff_chroma_pyramid")
+
+
+def chroma_tuning(S, f_lo, f_hi, bin_hz, edges, pitch_ws, mag_ws, tuning_index, n_pitches, threshold, counts):
+    """S (B, T, 1025) of music_stft; bins f_lo .. f_hi, bin_hz = sr / 2048; edges (101,) float64; pitch_ws, mag_ws
+    (B, T, f_hi - f_lo + 1) workspaces -> tuning_index, n_pitches (B,) int32, threshold (B,) fp32, counts (B, 100) int32.  One launch."""
+    B, T = S.shape[:2]
+    L.check(L.load().tcdiff_chroma_tuning(_p(S), B, T, f_lo, f_hi, bin_hz, _p(edges), _p(pitch_ws), _p(mag_ws), _p(tuning_index),
+                                          _p(n_pitches), _p(threshold), _p(counts), stream()), "tcdiff_chroma_tuning")
+
+
+def chroma_response(y, pyramid, tuning_index, tab, chroma, cqt_mag):
+    """y (B, n) fp32 view, its pyramid, tuning_index (B,) int32 on the device; tab: music._chroma_tables -> chroma (B, T, 12) and
+    (or None) cqt_mag (B, T, 252).  One launch."""
+    B, n = y.shape
+    L.check(L.load().tcdiff_chroma_response(_p(y), y.stride(0) if B > 1 else n, _p(pyramid), B, n, _p(tuning_index), _p(tab["twiddle"]),
+                                            _p(tab["basis"]), _p(tab["band"]), _p(tab["scale"]), _p(chroma), _p(cqt_mag), stream()),
+            "tcdiff_chroma_response")
+
+
 # ---- stick-figure frames ---------------------------------------------------------------------------------------------------
 def draw_project(joints, contacts, view, floor, up, contact_threshold, still, pts, trail, order, planted):
     """joints (b, dn, T, 24, 3) / contacts (b, dn, T, 4) fp32 views, read by their strides; view: 12 floats (row-major 3 x 4)"""
