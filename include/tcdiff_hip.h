@@ -1002,7 +1002,68 @@ int tcdiff_chroma_response(const float* y, long y_stride, const float* pyramid, 
                            const float* twiddle, const float* basis, const int* band, const float* scale, float* chroma, float* cqt_mag,
                            hipStream_t stream);
 
-/* ---- stick-figure frames (csrc/draw.hip) -----------------------------------------------------------------------------------
+/* ---- audio files: decode, downmix, resample (csrc/audio.hip) ---------------------------------------------------------------------
+ * What comes before the music features: librosa.load(wav_path, sr=30720) of dataset_utils.py:62, that is soundfile's decode to
+ * float32, librosa.to_mono and librosa.resample(res_type="kaiser_best", fix=True, scale=False) over resampy.resample, after
+ * data/slice.py:10-26 has cut the song into overlapping windows at the file's own rate (tcdiff_amd.audio.slice_audio, a view).
+ * Everything below restates soundfile / libsndfile, librosa 0.9.2 and resampy at those arguments FROM THEIR DEFINITIONS, not from
+ * their source, which is not available where this is built; like the rest of the music path, parity with their own output is not
+ * pinned.  The RIFF/WAVE container is parsed on the host (tcdiff_amd.audio.read_wav); only the data chunk's bytes reach the
+ * device.  Two launches for any number of clips, no host synchronisation, no atomics, every sum in a fixed order: a second run,
+ * and a clip computed alone, give the same bits.  Not built: containers other than little-endian RIFF/WAVE, writing the slices
+ * back as files, mono=False.
+ *
+ * tcdiff_audio_decode, one launch, one thread per frame.  data: clip b's data-chunk bytes at data + b * row_stride (row_stride a
+ * multiple of 4 and at least frames * channels * bytes rounded up to 4: samples are assembled from aligned dword loads, and the
+ * dword that holds a clip's last byte is read whole), interleaved little-endian frames of `channels` samples.  Per sample:
+ *   TC_AUDIO_U8   (b - 128) / 128          TC_AUDIO_S16  v / 2^15          TC_AUDIO_S24  v / 2^23        (two's complement v)
+ *   TC_AUDIO_S32  float32(v), round to nearest even, times 2^-31
+ *   TC_AUDIO_F32  as is                    TC_AUDIO_F64  rounded to float32, nearest even
+ * (all but S32 and F64 exact).  The downmix is numpy's float32 mean over the channels: s = x_0, then s = fl32(s + x_c) in channel
+ * order, then fl32(s / C), the division correctly rounded; with C = 1 the sample passes through unchanged.
+ * out [B][frames] float.
+ *
+ * tcdiff_audio_resample, one launch, one workgroup of 256 per 256 consecutive outputs of a clip.  y: clip b at y + b * y_stride,
+ * n floats (rows may overlap; positions outside a row are never read).  The HOST computes, in float64 with Python's expressions:
+ *   ratio = float(sr_new) / sr_orig;  n_out = int(n ratio);  size = int(ceil(n ratio));  inc = 1 / ratio;  scale = min(1, ratio);
+ *   step = int(scale 512)
+ * (at n = 735, 44100 -> 30720, n_out = 511 and size = 512; step is truncated, which gives down-sampling a DC gain slightly above
+ * 1: 1.0006 .. 1.0008 at 44100 -> 30720.  Both are the reference's and stay), and the table, N = 512 * 64, m = 0 .. N,
+ *   win[m]   = r sinc(r m / 512) kaiser(2 N + 1, beta = 14.769656459379492)[N + m],  r = 0.9475937167399596 (kaiser_best),
+ *              times ratio when ratio < 1;    delta[m] = win[m + 1] - win[m], delta[N] = 0
+ * in float64, rounded once to float32: table [N + 1][2] float (win, delta), DEVICE, 8-byte aligned.  Per output t < n_out, with
+ * nwin = N + 1:
+ *   tr = t inc;  n = (int)tr;  frac = scale (tr - n);  f = 512 frac;  off = (int)f;  eta = f - off
+ *   left :  i = 0 .. min(n + 1, (nwin - off) / step) - 1:      out[t] += (win[off + i step] + eta delta[off + i step]) y[n - i]
+ *   frac' = scale - frac;  f, off, eta again from frac'
+ *   right:  k = 0 .. min(n_orig - n - 1, (nwin - off) / step) - 1: out[t] += (win[off + k step] + eta delta[off + k step]) y[n + k + 1]
+ * (n_orig the clip's n).  tr = t inc is the form of resampy >= 0.3 and does not depend on evaluation order; resampy 0.2.2
+ * accumulates tr += inc instead.  The index arithmetic from tr to off and eta is float64 with one rounding per operation (no
+ * contraction), so n, off and both loop counts are the restatement's by construction; eta is then rounded to float32, and the
+ * weights, products and sums are float32 (fused multiply-adds, left wing then right wing, each in ascending i / k).
+ * out [B][size] float; out[t] = 0 for n_out <= t < size (librosa's fix_length).  The workgroup stages its span of the input in LDS
+ * ((int)(255 inc) + 3 + 2 ceil(nwin / step) floats, sized by the launcher: at most 3069 for sr_orig / sr_new <= 8) and deals its
+ * outputs to its threads in the order of off, which narrows a wave's table gathers and changes no output's bits; the table stays
+ * in global memory.
+ *
+ * TC_ERR_ARG for a NULL pointer, B < 1, frames / channels / n / n_out < 1, an unknown format, a row_stride too short, size < n_out,
+ * scale outside (0, 1], step outside [1, 512] or (n_out - 1) inc >= n; TC_ERR_ALIGN for data or row_stride not a multiple of 4
+ * or a table not 8-byte aligned; TC_ERR_UNSUPPORTED for B > 65535, channels > 65535, n or size >= 2^29, or step <
+ * TC_AUDIO_MIN_STEP (sr_orig / sr_new > 8). */
+#define TC_AUDIO_U8 0
+#define TC_AUDIO_S16 1
+#define TC_AUDIO_S24 2
+#define TC_AUDIO_S32 3
+#define TC_AUDIO_F32 4
+#define TC_AUDIO_F64 5
+#define TC_AUDIO_PRECISION 512       /* table entries per zero crossing */
+#define TC_AUDIO_TABLE (512 * 64 + 1)
+#define TC_AUDIO_MIN_STEP 64
+int tcdiff_audio_decode(const void* data, long row_stride, int B, int frames, int channels, int fmt, float* out, hipStream_t stream);
+int tcdiff_audio_resample(const float* y, long y_stride, int B, int n, const float* table, double inc, double scale, int step, int n_out,
+                          int size, float* out, hipStream_t stream);
+
+/* ---- stick-figure frames (csrc/draw.hip)-----------------------------------------------------------------------------------
  * What skeleton_render (vis.py:223-327) shows of a generated dance -- 23 bones per dancer, the root's trail on the floor and
  * four foot markers -- as RGB frames, in two launches for any number of clips: no host synchronisation, no atomics, a fixed
  * paint order, so the same input gives the same bits.

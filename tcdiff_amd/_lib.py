@@ -135,6 +135,8 @@ SET_MAX_D, SET_MAX_SWEEPS = 72, 30      # TC_SET_*
 MUSIC_N_FFT, MUSIC_HOP, MUSIC_N_MELS, MUSIC_N_MFCC, MUSIC_TEMPO_WIN, MUSIC_COLS = 2048, 512, 128, 20, 384, 425      # TC_MUSIC_*
 BEAT_WIN, BEAT_CHUNK, BEAT_TABLE = 480, 8, 480 * 480 - 1      # TC_BEAT_*
 CHROMA_BPO, CHROMA_OCTAVES, CHROMA_BINS, CHROMA_N, CHROMA_N_FFT, CHROMA_BAND, CHROMA_TUNINGS, CHROMA_TAPS = 36, 7, 252, 12, 1024, 24, 100, 63      # TC_CHROMA_*
+AUDIO_FMT = {"u8": 0, "s16": 1, "s24": 2, "s32": 3, "f32": 4, "f64": 5}      # TC_AUDIO_U8 .. TC_AUDIO_F64
+AUDIO_PRECISION, AUDIO_TABLE, AUDIO_MIN_STEP = 512, 512 * 64 + 1, 64      # TC_AUDIO_*
 
 _SIGS = {
     "tcdiff_gemm_tile": [_i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, C.POINTER(TileEpi), _vp],
@@ -212,6 +214,9 @@ _SIGS = {
     "tcdiff_chroma_pyramid": [_vp, _l, _i, _i, _vp, _vp, _vp],
     "tcdiff_chroma_tuning": [_vp, _i, _i, _i, _i, _f] + [_vp] * 8,
     "tcdiff_chroma_response": [_vp, _l, _vp, _i, _i] + [_vp] * 8,
+    # audio files: decode, downmix, resample (csrc/audio.hip)
+    "tcdiff_audio_decode": [_vp, _l, _i, _i, _i, _i, _vp, _vp],
+    "tcdiff_audio_resample": [_vp, _l, _i, _i, _vp, C.c_double, C.c_double, _i, _i, _i, _vp, _vp],
     # stick-figure frames (csrc/draw.hip)
     "tcdiff_draw_project": [_vp, C.POINTER(_l), _vp, C.POINTER(_l), _i, _i, _i, C.POINTER(_f), _f, _i, C.c_double, C.c_double, _vp, _vp,
                             _vp, _vp, _vp],

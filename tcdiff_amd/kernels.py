@@ -664,6 +664,23 @@ def chroma_response(y, pyramid, tuning_index, tab, chroma, cqt_mag):
             "tcdiff_chroma_response")
 
 
+# ---- audio files: decode, downmix, resample ----------------------------------------------------------------------------------
+def audio_decode(data, frames, channels, fmt, out):
+    """data (B, row_stride) uint8, each row a file's data-chunk bytes (row_stride a multiple of 4); fmt: a key of _lib.AUDIO_FMT
+    -> out (B, frames) fp32 mono.  One launch."""
+    B = data.shape[0]
+    L.check(L.load().tcdiff_audio_decode(_p(data), data.stride(0), B, frames, channels, L.AUDIO_FMT[fmt], _p(out), stream()),
+            "tcdiff_audio_decode")
+
+
+def audio_resample(y, table, inc, scale, step, n_out, out):
+    """y (B, n) fp32 view read through its row stride (rows may overlap); table (32769, 2) fp32 (win, delta); inc, scale float64
+    and step as the header defines them -> out (B, size) fp32, samples n_out .. size - 1 zero.  One launch."""
+    B, n = y.shape
+    L.check(L.load().tcdiff_audio_resample(_p(y), y.stride(0) if B > 1 else n, B, n, _p(table), inc, scale, step, n_out, out.shape[1],
+                                           _p(out), stream()), "tcdiff_audio_resample")
+
+
 # ---- stick-figure frames ---------------------------------------------------------------------------------------------------
 def draw_project(joints, contacts, view, floor, up, contact_threshold, still, pts, trail, order, planted):
     """joints (b, dn, T, 24, 3) / contacts (b, dn, T, 4) fp32 views, read by their strides; view: 12 floats (row-major 3 x 4)"""

@@ -3,7 +3,10 @@
 
     cond = music_cond(audio)                               # (B, T, 438), the layout every entry point of this package reads
 
-The caller brings samples at ``sr`` (decoding and resampling audio files is not part of this).  The parts, each callable alone:
+    cond = wav_cond("song.wav", slices=(0.5, 5.0))         # the same from a WAV file on disk, one row per 5-second slice
+
+``audio`` holds samples at ``sr``; ``tcdiff_amd.audio`` brings them from a WAV file (decode, downmix, the slicing of
+data/slice.py, resampling to 30720 Hz: two more launches).  The parts, each callable alone:
 
     feats, parts = music_features(audio, return_parts=True)    # (B, T, 425): mfcc, delta, onset_env, tempogram; eleven launches
     tempo, onset_beat = beat_track(parts["onset_env"])     # (B,) float64 beats per minute, (B, T) one-hot: two more launches
@@ -21,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import audio
 from . import kernels as K
 
 N_FFT, HOP, N_BINS, N_MELS, N_MFCC, TEMPO_WIN, N_COLS = L.MUSIC_N_FFT, L.MUSIC_HOP, L.MUSIC_N_FFT // 2 + 1, L.MUSIC_N_MELS, \
@@ -452,6 +456,13 @@ def music_cond(audio, chroma=None, *, sr=30720) -> torch.Tensor:
     if chroma is None:
         chroma = chroma_cqt(parts["harmonic"], sr=sr)
     return assemble_cond(feats, chroma, onset_beat)
+
+
+def wav_cond(files, *, slices=None, sr=30720, device="cuda:0") -> torch.Tensor:
+    """WAV files (paths, bytes or ``audio.WavData``; see ``audio.load_audio``) -> cond (B, T, 438): ``music_cond`` of
+    ``audio.load_audio(files, sr=sr, slices=slices)``, the reference's ``librosa.load(wav_path, sr=30720)`` in front of its feature
+    extraction.  With ``slices=(stride, length)`` in seconds the rows are the slices of one file."""
+    return music_cond(audio.load_audio(files, sr=sr, slices=slices, device=device), sr=sr)
 
 
 def assemble_cond(stft_feats, chroma, onset_beat) -> torch.Tensor:
