@@ -1,0 +1,133 @@
+"""The C ABI of libtcdiff_gfx950.so, read from include/tcdiff_hip.h: its integer macros, structs and prototypes as ctypes.
+
+The header is the one place where the ABI is written down; _lib.py binds the library from what parse() returns.  The parser
+knows the C that the header uses and nothing more, and it never guesses: a declaration it does not recognise raises
+TcdiffError with the header line.  Imports neither torch nor the library.
+"""
+import ctypes as C
+import os
+import re
+from collections import namedtuple
+
+HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "tcdiff_hip.h")
+
+
+class TcdiffError(RuntimeError):
+    pass
+
+
+SCALARS = {"int": C.c_int, "long": C.c_long, "float": C.c_float, "double": C.c_double, "uint32_t": C.c_uint32,
+           "uint64_t": C.c_uint64, "unsigned char": C.c_ubyte, "unsigned": C.c_uint, "hipStream_t": C.c_void_p}
+
+# constants {macro: int}; structs {C name: ctypes.Structure class}; functions {name: (restype, argtypes, the parameters' C types)}
+Abi = namedtuple("Abi", "constants structs functions")
+
+_INT = r"0[xX][0-9a-fA-F]+|0|[1-9]\d*"
+_PREPROCESSOR = re.compile(r"^[ \t]*#[^\n]*", re.M)
+_DEFINE = re.compile(r"[ \t]*#[ \t]*define[ \t]+(\w+)(\(?)(.*)")
+_DECLARATOR = re.compile(r"\s*(\**)\s*(\w*)\s*((?:\[\s*\w*\s*\]\s*)*)")
+_STRUCT = re.compile(r"\s*typedef\s+struct\s*\w*\s*\{(.*)\}\s*(\w+)\s*", re.S)
+_FUNCTION = re.compile(r"\s*(int|const\s+char\s*\*)\s*(tcdiff_\w+)\s*\((.*)\)\s*", re.S)
+_STREAM = re.compile(r"\s*typedef\s+struct\s+\w+\s*\*\s*hipStream_t\s*")
+
+
+def _blank(m):
+    """what replaces a match that is dropped: a blank and the match's line ends, so that every later offset stays on its line"""
+    return " " + "\n" * m.group().count("\n")
+
+
+def parse(text: str, name: str = "include/tcdiff_hip.h") -> Abi:
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", _blank, text, flags=re.S)
+    constants, structs, functions = {}, {}, {}
+    types = dict(SCALARS, void=None)          # C type -> ctypes type; the structs join as they are declared
+
+    def type_re():
+        return re.compile(r"\s*(const\s+)?(" + "|".join(sorted(types, key=len, reverse=True)) + r")\b")
+    a_type = type_re()
+
+    def fail(pos, what, decl):
+        pos += len(text[pos:]) - len(text[pos:].lstrip())
+        raise TcdiffError(f"{name}:{text.count(chr(10), 0, pos) + 1}: {what}: {' '.join(decl.split())!r}")
+
+    def integer(expr, pos, decl):
+        toks = [str(constants.get(t, t)) for t in re.findall(_INT + r"|[-+*()]|[^\s+*()-]+", expr)]
+        bad = [t for t in toks if not re.fullmatch(_INT + r"|[-+*()]", t)]
+        if bad or not toks:
+            fail(pos, f"{bad[0] if bad else 'nothing'!r} where an integer expression of literals, ( ) + - * is expected", decl)
+        try:
+            return int(eval(" ".join(toks), {"__builtins__": {}}))
+        except (SyntaxError, TypeError):
+            fail(pos, "malformed integer expression", decl)
+
+    def declarators(decl, pos):
+        """'const float* a, *b[3]' -> (ctypes type, C type, name, dimensions) of a and of b; an unsized dimension is None"""
+        t = a_type.match(decl)
+        if not t:
+            fail(pos, f"unknown type {' '.join(decl.split()[:2])!r}", decl)
+        base, out = types[t.group(2)], []
+        for d in decl[t.end():].split(","):
+            m = _DECLARATOR.fullmatch(d)
+            if not m or (base is None and not m.group(1)):
+                fail(pos, f"unknown declarator {d.strip()!r}", decl)
+            dims = [integer(n, pos, decl) if n else None for n in re.findall(r"\[\s*(\w*)\s*\]", m.group(3))]
+            out.append((C.c_void_p if m.group(1) else base, ("const " if t.group(1) else "") + t.group(2) + m.group(1), m.group(2), dims))
+        return out
+
+    def struct(body, cname, pos):
+        fields = []
+        for m in re.finditer(r"[^;]*[^;\s][^;]*", body):
+            for ctype, _, ident, dims in declarators(m.group(), pos + m.start()):
+                if not ident or None in dims:
+                    fail(pos + m.start(), "a field needs a name and sized dimensions", m.group())
+                for n in reversed(dims):
+                    ctype = ctype * n
+                fields.append((ident, ctype))
+        nonlocal a_type
+        structs[cname] = types[cname] = type(cname, (C.Structure,), {"_fields_": fields})
+        a_type = type_re()
+
+    def function(ret, fname, params, pos, decl):
+        args = []
+        for p in [] if params.strip() == "void" else params.split(","):
+            if "(" in p:
+                fail(pos, f"unknown parameter {p.strip()!r}", decl)
+            (ctype, ctext, _, dims), = declarators(p, pos)
+            args.append((C.c_void_p, ctext + "*") if dims else (ctype, ctext))      # an array parameter is a pointer
+        functions[fname] = (C.c_int if ret == "int" else C.c_char_p, [a for a, _ in args], [c for _, c in args])
+
+    # preprocessor lines: the object-like TC_* macros are the constants, everything else is skipped
+    for m in _PREPROCESSOR.finditer(text):
+        d = _DEFINE.fullmatch(m.group())
+        if d and d.group(1).startswith("TC_") and not d.group(2):
+            constants[d.group(1)] = integer(d.group(3), m.start(), m.group())
+    text = _PREPROCESSOR.sub(_blank, text)
+    text, externs = re.subn(r'extern\s+"C"\s*\{', _blank, text)
+
+    # declarations: a statement ends at a ';' outside braces
+    depth, start = 0, 0
+    for m in re.finditer(r"[{};]", text):
+        if m.group() == "{":
+            depth += 1
+        elif m.group() == "}" and depth == 0 and externs and not text[start:m.start()].strip():
+            externs, start = externs - 1, m.end()          # the end of an extern "C" block
+        elif m.group() == "}":
+            depth -= 1
+            if depth < 0:
+                fail(m.start(), "unbalanced braces", text[start:m.end()])
+        elif depth == 0:
+            decl, pos, start = text[start:m.start()], start, m.end()
+            s, f = _STRUCT.fullmatch(decl), _FUNCTION.fullmatch(decl)
+            if s:
+                struct(s.group(1), s.group(2), pos + s.start(1))
+            elif f:
+                function(f.group(1), f.group(2), f.group(3), pos, decl)
+            elif not _STREAM.fullmatch(decl):
+                fail(pos, "unknown declaration", decl)
+    if depth or text[start:].strip():
+        fail(start, "unterminated declaration", text[start:][:200])
+    return Abi(constants, structs, functions)
+
+
+def load() -> Abi:
+    with open(HEADER) as f:
+        return parse(f.read())

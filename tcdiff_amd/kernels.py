@@ -66,6 +66,16 @@ def _p(t):
     return None if t is None else t.data_ptr()
 
 
+def _row_stride(y):
+    """row stride of a (B, n) view; a single row counts as contiguous, whatever stride the view carries for it"""
+    return y.stride(0) if y.shape[0] > 1 else y.shape[1]
+
+
+def _skeleton(parents, offsets=()):
+    """the FK launchers' HOST skeleton arguments: int[24] parents and float[24][3] offsets"""
+    return (C.c_int * 24)(*[int(p) for p in parents]), (C.c_float * 72)(*[float(v) for row in offsets for v in row])
+
+
 def gemm_tile(dt, A, W, M, N, K, *, lda=None, ldw=None, A2=None, split_n=0, a_mod=0, mode=L.EPI_STORE_T,
               act=L.ACT_NONE, bias=None, out=None, ldc=0, out_k=None, out_v=None, scale_q=1.0, Lseq=0, Lp=0, H=0,
               n_q=0, n_k=0, tok_off=0, seq_off=0, out2=None, ldc2=0, act_src=None, ld_src=0, act2=L.ACT_NONE, seed=None,
@@ -320,9 +330,7 @@ def ax_from_6v(rot6d, n_rows, per_row, row_stride, out):
 
 
 def smpl_fk(axis_angle, root, n, parents, offsets, joints):
-    par = (C.c_int * 24)(*[int(p) for p in parents])
-    off = (C.c_float * 72)(*[float(v) for row in offsets for v in row])
-    L.check(L.load().tcdiff_smpl_fk(_p(axis_angle), _p(root), n, par, off, _p(joints), stream()), "tcdiff_smpl_fk")
+    L.check(L.load().tcdiff_smpl_fk(_p(axis_angle), _p(root), n, *_skeleton(parents, offsets), _p(joints), stream()), "tcdiff_smpl_fk")
 
 
 def loss_terms(model_out, x_start, joints_model, joints_target, p2_weight, t, out, b, dn, S, Cn, l1):
@@ -347,8 +355,9 @@ def adan_step(table, scalars):
 
 
 # ---- the Navigator's loss head and optimizer (csrc/navigator_step.hip) -------------------------------------------------
-def _strides4(t):
-    return (C.c_long * 4)(*t.stride())
+def _strides(t, n):
+    """the first n strides of a view as the HOST long[n] a launcher reads them from; no view (None) stays NULL"""
+    return None if t is None else (C.c_long * n)(*t.stride()[:n])
 
 
 def nav_loss_blocks(n_elements: int) -> int:
@@ -359,13 +368,13 @@ def nav_loss_blocks(n_elements: int) -> int:
 def nav_loss(pre, tgt, partial, out):
     """pre, tgt: (b, dn, seq, 2) fp32 views, read by their strides; out [4] = total, recon, dis, v"""
     b, dn, seq, _ = pre.shape
-    L.check(L.load().tcdiff_nav_loss(_p(pre), _strides4(pre), _p(tgt), _strides4(tgt), b, dn, seq, _p(partial), _p(out),
+    L.check(L.load().tcdiff_nav_loss(_p(pre), _strides(pre, 4), _p(tgt), _strides(tgt, 4), b, dn, seq, _p(partial), _p(out),
                                      stream()), "tcdiff_nav_loss")
 
 
 def nav_loss_bwd(pre, tgt, grad_out, d_pre):
     b, dn, seq, _ = pre.shape
-    L.check(L.load().tcdiff_nav_loss_bwd(_p(pre), _strides4(pre), _p(tgt), _strides4(tgt), b, dn, seq, _p(grad_out), _p(d_pre),
+    L.check(L.load().tcdiff_nav_loss_bwd(_p(pre), _strides(pre, 4), _p(tgt), _strides(tgt, 4), b, dn, seq, _p(grad_out), _p(d_pre),
                                          stream()), "tcdiff_nav_loss_bwd")
 
 
@@ -531,24 +540,18 @@ def loss_terms_bwd(model_out, x_start, joints_model, joints_target, p2_weight, t
 
 
 def fk_bwd(motion, d_joints, n, Cn, parents, offsets, d_out):
-    par = (C.c_int * 24)(*[int(p) for p in parents])
-    off = (C.c_float * 72)(*[float(v) for row in offsets for v in row])
-    L.check(L.load().tcdiff_fk_bwd(_p(motion), _p(d_joints), n, Cn, par, off, _p(d_out), stream()), "tcdiff_fk_bwd")
+    L.check(L.load().tcdiff_fk_bwd(_p(motion), _p(d_joints), n, Cn, *_skeleton(parents, offsets), _p(d_out), stream()), "tcdiff_fk_bwd")
 
 
 # ---- render-time pose export ---------------------------------------------------------------------------------------------
 def pose_export(samples, b, S, dn, mode, scale, min_, fade, parents, offsets, smpl_trans, smpl_poses, full_pose, contact):
-    par = (C.c_int * 24)(*[int(p) for p in parents])
-    off = (C.c_float * 72)(*[float(v) for row in offsets for v in row])
-    L.check(L.load().tcdiff_pose_export(_p(samples), b, S, dn, mode, _p(scale), _p(min_), _p(fade), par, off, _p(smpl_trans),
+    L.check(L.load().tcdiff_pose_export(_p(samples), b, S, dn, mode, _p(scale), _p(min_), _p(fade), *_skeleton(parents, offsets), _p(smpl_trans),
                                         _p(smpl_poses), _p(full_pose), _p(contact), stream()), "tcdiff_pose_export")
 
 
 # ---- motion ingest -------------------------------------------------------------------------------------------------------
 def motion_ingest(pos, q, clips, dn, sq, parents, offsets, fit, scale, min_, feats, raw, feet, stats):
-    par = (C.c_int * 24)(*[int(p) for p in parents])
-    off = (C.c_float * 72)(*[float(v) for row in offsets for v in row])
-    L.check(L.load().tcdiff_motion_ingest(_p(pos), _p(q), clips, dn, sq, par, off, int(bool(fit)), _p(scale), _p(min_), _p(feats),
+    L.check(L.load().tcdiff_motion_ingest(_p(pos), _p(q), clips, dn, sq, *_skeleton(parents, offsets), int(bool(fit)), _p(scale), _p(min_), _p(feats),
                                           _p(raw), _p(feet), _p(stats), stream()), "tcdiff_motion_ingest")
 
 
@@ -557,20 +560,17 @@ def motion_metrics(joints, contacts, beats, up, fps, contact_threshold, still, r
                    contact_slide, contact_break, contact_frames, collision_rate, beat_align, motion_beats):
     """joints (b, dn, T, 24, 3) / contacts (b, dn, T, 4) fp32 views, read by their strides; beats (b, T) uint8 contiguous"""
     b, dn, T = joints.shape[:3]
-    js = (C.c_long * 3)(*joints.stride()[:3])
-    cs = None if contacts is None else (C.c_long * 3)(*contacts.stride()[:3])
-    L.check(L.load().tcdiff_motion_metrics(_p(joints), js, _p(contacts), cs, _p(beats), b, dn, T, up, fps, contact_threshold, still,
-                                           radius, sigma_smooth, sigma_beat, _p(ws), _p(iws), _p(pfc), _p(contact_slide),
-                                           _p(contact_break), _p(contact_frames), _p(collision_rate), _p(beat_align),
-                                           _p(motion_beats), stream()), "tcdiff_motion_metrics")
+    L.check(L.load().tcdiff_motion_metrics(_p(joints), _strides(joints, 3), _p(contacts), _strides(contacts, 3), _p(beats), b, dn, T, up, fps,
+                                           contact_threshold, still, radius, sigma_smooth, sigma_beat, _p(ws), _p(iws), _p(pfc), _p(contact_slide),
+                                           _p(contact_break), _p(contact_frames), _p(collision_rate), _p(beat_align), _p(motion_beats), stream()),
+            "tcdiff_motion_metrics")
 
 
 # ---- set-level metrics -----------------------------------------------------------------------------------------------------
 def kinetic_features(joints, up, window, fps, feats):
     """joints (b, dn, T, 24, 3) fp32 view, read by its strides; feats (b, dn, 72) float64 contiguous"""
     b, dn, T = joints.shape[:3]
-    js = (C.c_long * 3)(*joints.stride()[:3])
-    L.check(L.load().tcdiff_kinetic_features(_p(joints), js, b, dn, T, up, window, fps, _p(feats), stream()),
+    L.check(L.load().tcdiff_kinetic_features(_p(joints), _strides(joints, 3), b, dn, T, up, window, fps, _p(feats), stream()),
             "tcdiff_kinetic_features")
 
 
@@ -596,8 +596,8 @@ def music_stft(y, tab, D, S, M, frame_max):
     """y (B, n) fp32 view read through its row stride; tab: music._tables; D (B, T, 1025, 2) and S (B, T, 1025), both or neither;
     M (B, T, 128) and its maximum per frame, frame_max (B, T)"""
     B, n = y.shape
-    L.check(L.load().tcdiff_music_stft(_p(y), y.stride(0) if B > 1 else n, B, n, _p(tab["twiddle"]), _p(tab["window"]), _p(tab["mel_w"]),
-                                       _p(tab["mel_range"]), _p(D), _p(S), _p(M), _p(frame_max), stream()), "tcdiff_music_stft")
+    L.check(L.load().tcdiff_music_stft(_p(y), _row_stride(y), B, n, _p(tab["twiddle"]), _p(tab["window"]), _p(tab["mel_w"]), _p(tab["mel_range"]),
+                                       _p(D), _p(S), _p(M), _p(frame_max), stream()), "tcdiff_music_stft")
 
 
 def music_mfcc(M, frame_max, tab, mx, mel_db, feats):
@@ -624,7 +624,7 @@ def music_onset(M, frame_max, tab, mx, onset_env, feats):
 def beat_tempo(o, window, partial):
     """o (B, T) fp32 view read through its row stride; window (480,) fp32 -> partial (B, ceil(T / 8), 480) float64.  One launch."""
     B, T = o.shape
-    L.check(L.load().tcdiff_beat_tempo(_p(o), o.stride(0) if B > 1 else T, B, T, _p(window), _p(partial), stream()), "tcdiff_beat_tempo")
+    L.check(L.load().tcdiff_beat_tempo(_p(o), _row_stride(o), B, T, _p(window), _p(partial), stream()), "tcdiff_beat_tempo")
 
 
 def beat_track(o, partial, prior, tables, period_host, trim, local_score, cum_score, backlink, beats_ws, onset_beat, period, n_beats, tempo):
@@ -634,9 +634,9 @@ def beat_track(o, partial, prior, tables, period_host, trim, local_score, cum_sc
     One launch."""
     B, T = o.shape
     ph = None if period_host is None else (C.c_int * B)(*[int(p) for p in period_host])
-    L.check(L.load().tcdiff_beat_track(_p(o), o.stride(0) if B > 1 else T, B, T, _p(partial), _p(prior), _p(tables), ph, int(bool(trim)),
-                                       _p(local_score), _p(cum_score), _p(backlink), _p(beats_ws), _p(onset_beat), _p(period), _p(n_beats),
-                                       _p(tempo), stream()), "tcdiff_beat_track")
+    L.check(L.load().tcdiff_beat_track(_p(o), _row_stride(o), B, T, _p(partial), _p(prior), _p(tables), ph, int(bool(trim)), _p(local_score),
+                                       _p(cum_score), _p(backlink), _p(beats_ws), _p(onset_beat), _p(period), _p(n_beats), _p(tempo), stream()),
+            "tcdiff_beat_track")
 
 
 # ---- music features: the chroma columns --------------------------------------------------------------------------------------
@@ -644,7 +644,7 @@ def chroma_pyramid(y, taps, pyramid):
     """y (B, n) fp32 view read through its row stride; taps (63,) fp32 -> pyramid (B, sum_s ceil(n / 2^s)), the six decimated
     signals one after another.  One launch."""
     B, n = y.shape
-    L.check(L.load().tcdiff_chroma_pyramid(_p(y), y.stride(0) if B > 1 else n, B, n, _p(taps), _p(pyramid), stream()), "tcdiff_chroma_pyramid")
+    L.check(L.load().tcdiff_chroma_pyramid(_p(y), _row_stride(y), B, n, _p(taps), _p(pyramid), stream()), "tcdiff_chroma_pyramid")
 
 
 def chroma_tuning(S, f_lo, f_hi, bin_hz, edges, pitch_ws, mag_ws, tuning_index, n_pitches, threshold, counts):
@@ -659,9 +659,8 @@ def chroma_response(y, pyramid, tuning_index, tab, chroma, cqt_mag):
     """y (B, n) fp32 view, its pyramid, tuning_index (B,) int32 on the device; tab: music._chroma_tables -> chroma (B, T, 12) and
     (or None) cqt_mag (B, T, 252).  One launch."""
     B, n = y.shape
-    L.check(L.load().tcdiff_chroma_response(_p(y), y.stride(0) if B > 1 else n, _p(pyramid), B, n, _p(tuning_index), _p(tab["twiddle"]),
-                                            _p(tab["basis"]), _p(tab["band"]), _p(tab["scale"]), _p(chroma), _p(cqt_mag), stream()),
-            "tcdiff_chroma_response")
+    L.check(L.load().tcdiff_chroma_response(_p(y), _row_stride(y), _p(pyramid), B, n, _p(tuning_index), _p(tab["twiddle"]), _p(tab["basis"]),
+                                            _p(tab["band"]), _p(tab["scale"]), _p(chroma), _p(cqt_mag), stream()), "tcdiff_chroma_response")
 
 
 # ---- audio files: decode, downmix, resample ----------------------------------------------------------------------------------
@@ -677,24 +676,22 @@ def audio_resample(y, table, inc, scale, step, n_out, out):
     """y (B, n) fp32 view read through its row stride (rows may overlap); table (32769, 2) fp32 (win, delta); inc, scale float64
     and step as the header defines them -> out (B, size) fp32, samples n_out .. size - 1 zero.  One launch."""
     B, n = y.shape
-    L.check(L.load().tcdiff_audio_resample(_p(y), y.stride(0) if B > 1 else n, B, n, _p(table), inc, scale, step, n_out, out.shape[1],
-                                           _p(out), stream()), "tcdiff_audio_resample")
+    L.check(L.load().tcdiff_audio_resample(_p(y), _row_stride(y), B, n, _p(table), inc, scale, step, n_out, out.shape[1], _p(out), stream()),
+            "tcdiff_audio_resample")
 
 
 # ---- stick-figure frames ---------------------------------------------------------------------------------------------------
 def draw_project(joints, contacts, view, floor, up, contact_threshold, still, pts, trail, order, planted):
     """joints (b, dn, T, 24, 3) / contacts (b, dn, T, 4) fp32 views, read by their strides; view: 12 floats (row-major 3 x 4)"""
     b, dn, T = joints.shape[:3]
-    js = (C.c_long * 3)(*joints.stride()[:3])
-    cs = None if contacts is None else (C.c_long * 3)(*contacts.stride()[:3])
     v = None if view is None else (C.c_float * 12)(*[float(x) for x in view])
-    L.check(L.load().tcdiff_draw_project(_p(joints), js, _p(contacts), cs, b, dn, T, v, floor, up, contact_threshold, still, _p(pts),
-                                         _p(trail), _p(order), _p(planted), stream()), "tcdiff_draw_project")
+    L.check(L.load().tcdiff_draw_project(_p(joints), _strides(joints, 3), _p(contacts), _strides(contacts, 3), b, dn, T, v, floor, up,
+                                         contact_threshold, still, _p(pts), _p(trail), _p(order), _p(planted), stream()), "tcdiff_draw_project")
 
 
 def draw_raster(pts, trail, order, planted, b, dn, T, W, H, parents, static_segs, n_static, colors, n_colors, style, frames):
     """style: an _lib.DrawStyle; frames: a uint8 tensor or a device address (frames placed inside a larger buffer)"""
-    par = None if parents is None else (C.c_int * 24)(*[int(p) for p in parents])
+    par = None if parents is None else _skeleton(parents)[0]
     out = frames if frames is None or isinstance(frames, int) else frames.data_ptr()
     L.check(L.load().tcdiff_draw_raster(_p(pts), _p(trail), _p(order), _p(planted), b, dn, T, W, H, par, _p(static_segs), n_static,
                                         _p(colors), n_colors, None if style is None else C.byref(style), out, stream()),

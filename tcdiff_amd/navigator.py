@@ -436,7 +436,6 @@ def site_block(i: int, k: int) -> int:
     return 260 + 4 * i + k
 
 
-_WG_CHUNKS, _WG_PARTIAL = 32, 448 * 896 + 448          # TC_NAV_WG_CHUNKS, TC_NAV_WG_PARTIAL
 _G_MUSIC = 438 * 876 + 438 + 438 * 438 + 438 + 64 * 438 + 64 + 64 * 64 + 64
 _G_LSTM = 256 * (2 + 64 + 2) + 2 * 256 * (64 + 64 + 2)
 
@@ -526,7 +525,7 @@ class TrajTrainer:
                       dec_z=z(R, 320), mus_z=z(P, 896), d_out=z(R, 2), gx=z(R, 128), g_dec=z(R, 336), g_mpb=z(R, 64),
                       g_m=z(R, 128), g_hid=z(R, 512), g_a=z(R, 128), g_o=z(b, Tp, 128), delta=z(b, 4, Tp), g_qkv=z(R, 384),
                       n1=z(R, 128), n2=z(R, 128), ln_part=z(b * (Tp // 16), 4, 128), g_me=z(P, 64), g_mp=z(P, 64), g_mz=z(P, 896),
-                      g_gates=z(3, R, 256), partial=z(_WG_CHUNKS, _WG_PARTIAL))
+                      g_gates=z(3, R, 256), partial=z(L.NAV_WG_CHUNKS, L.NAV_WG_PARTIAL))
             if len(self._plans) >= 2:
                 self._plans.clear()
             self._plans[key] = pl

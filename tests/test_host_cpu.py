@@ -3,13 +3,15 @@ validation happens before any launch, the host classes mirror the reference's pa
 tables, and the product path refuses to run off-GPU (no CPU fallback)."""
 import ctypes
 import os
-import re
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+from tcdiff_amd import _abi
 from tcdiff_amd import _lib as L
 from tcdiff_amd.diffusion import GaussianDiffusion
 from tcdiff_amd.model import DanceDecoder
@@ -24,13 +26,23 @@ def lib():
     return L.load()
 
 
+def _dynamic_symbols(path):
+    """the names the shared library defines in its dynamic symbol table, read with binutils nm or ROCm's llvm-readelf"""
+    if shutil.which("nm"):
+        out = subprocess.run(["nm", "-D", "--defined-only", path], check=True, capture_output=True, text=True).stdout
+        return {ln.split()[-1].split("@")[0] for ln in out.splitlines() if ln.split()}
+    out = subprocess.run(["/opt/rocm/llvm/bin/llvm-readelf", "--dyn-syms", "-W", path], check=True, capture_output=True, text=True).stdout
+    rows = [ln.split() for ln in out.splitlines()]
+    return {r[7].split("@")[0] for r in rows if len(r) == 8 and r[0].rstrip(":").isdigit() and r[6] != "UND"}
+
+
 def test_library_exports_every_declared_symbol(lib):
-    hdr = open(os.path.join(ROOT, "include", "tcdiff_hip.h")).read()
-    declared = sorted(set(re.findall(r"\b(tcdiff_[a-z_0-9]+)\s*\(", hdr)))
-    assert len(declared) >= 16
-    for name in declared:
+    """EXPORTS is parsed from the header, so the header cannot judge it: the built library's own symbol table does, both ways"""
+    defined = sorted(n for n in _dynamic_symbols(L.LIB_PATH) if n.startswith("tcdiff_"))
+    assert len(defined) >= 79
+    assert sorted(L.EXPORTS) == defined
+    for name in defined:
         assert hasattr(lib, name), f"{name} declared in include/tcdiff_hip.h but not exported"
-    assert sorted(L.EXPORTS) == declared
     assert b"gfx950" in lib.tcdiff_version()
 
 
@@ -52,30 +64,59 @@ def test_argument_validation_without_gpu(lib):
         L.check(-2, "x")
 
 
+def _fields(cls, prefix=""):
+    """(C member designator, offset) of every field of a ctypes structure, struct-typed members (and their arrays) descended into"""
+    for name, ctype in cls._fields_:
+        off = getattr(cls, name).offset
+        yield prefix + name, off
+        elem, n = (ctype._type_, ctype._length_) if issubclass(ctype, ctypes.Array) else (ctype, 0)
+        if issubclass(elem, ctypes.Structure):
+            for i in range(max(n, 1)):
+                for sub, o in _fields(elem, f"{prefix}{name}[{i}]." if n else f"{prefix}{name}."):
+                    yield sub, off + i * ctypes.sizeof(elem) + o
+
+
 def test_ctypes_structures_match_the_header(tmp_path):
-    """The argument structures cross the C ABI by value / by pointer: the ctypes mirrors in _lib.py must have the header's sizes and
-    (for the largest one) field offsets -- checked with the C compiler itself."""
-    import shutil
-    import subprocess
+    """What _abi.py reads from the header, judged by the C compiler reading the same header: sizeof of every struct, offsetof of every
+    field, the value of every integer macro -- and a translation unit, compiled with -Werror, that calls every launcher with one
+    argument per parsed parameter, each cast to its parsed C type, and assigns it to a function pointer of the parsed signature."""
     if shutil.which("gcc") is None or not os.path.isdir("/opt/rocm/include"):
         pytest.skip("needs gcc and the HIP headers")
-    pairs = [("tcdiff_tile_epi", L.TileEpi), ("tcdiff_row_epi", L.RowEpi), ("tcdiff_chain_args", L.ChainArgs),
-             ("tcdiff_step_prologue_args", L.StepPrologueArgs), ("tcdiff_row_args", L.RowArgs), ("tcdiff_ct_desc", L.CtDesc),
-             ("tcdiff_ws_desc", L.WsDesc), ("tcdiff_tn_problem", L.TnProblem), ("tcdiff_adan_scalars", L.AdanScalars)]
-    chain_fields = [f[0] for f in L.ChainArgs._fields_]
-    src = ['#include <stdio.h>', '#include <stddef.h>', '#include "tcdiff_hip.h"', "int main(void) {"]
-    src += [f'  printf("%zu\\n", sizeof({c}));' for c, _ in pairs]
-    src += [f'  printf("%zu\\n", offsetof(tcdiff_chain_args, {f}));' for f in chain_fields]
+    abi = L.ABI
+    assert len(abi.structs) == 17 and len(abi.functions) == 79 and len(abi.constants) >= 70
+    want, src = [], ['#include <stdio.h>', '#include <stddef.h>', '#include "tcdiff_hip.h"', "int main(void) {"]
+    for cname, cls in abi.structs.items():
+        want.append((f"sizeof({cname})", ctypes.sizeof(cls)))
+        src.append(f'  printf("%zu\\n", sizeof({cname}));')
+        for member, off in _fields(cls):
+            want.append((f"offsetof({cname}, {member})", off))
+            src.append(f'  printf("%zu\\n", offsetof({cname}, {member}));')
+    for macro, value in abi.constants.items():
+        want.append((macro, value))
+        src.append(f'  printf("%ld\\n", (long)({macro}));')
     src += ["  return 0;", "}"]
+    cc = ["gcc", "-I", os.path.join(ROOT, "include"), "-I", "/opt/rocm/include", "-D__HIP_PLATFORM_AMD__"]
     cfile, exe = tmp_path / "abi.c", tmp_path / "abi"
     cfile.write_text("\n".join(src))
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), "-I", "/opt/rocm/include", "-D__HIP_PLATFORM_AMD__", str(cfile),
-                    "-o", str(exe)], check=True, capture_output=True)
+    subprocess.run(cc + [str(cfile), "-o", str(exe)], check=True, capture_output=True)
     out = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    for (cname, cls), size in zip(pairs, out):
-        assert ctypes.sizeof(cls) == size, f"{cname}: header {size} bytes, ctypes mirror {ctypes.sizeof(cls)}"
-    for f, off in zip(chain_fields, out[len(pairs):]):
-        assert getattr(L.ChainArgs, f).offset == off, f"tcdiff_chain_args.{f}: header offset {off}, ctypes {getattr(L.ChainArgs, f).offset}"
+    assert len(out) == len(want)
+    for (what, mine), theirs in zip(want, out):
+        print(what, theirs)
+        assert mine == theirs, f"{what}: the C compiler says {theirs}, the parsed header {mine}"
+
+    calls = ['#include "tcdiff_hip.h"', "volatile int z;", "void call_every_launcher(void) {"]
+    for fname, (restype, argtypes, ctexts) in abi.functions.items():
+        assert argtypes == [ctypes.c_void_p if c.endswith("*") else _abi.SCALARS[c] for c in ctexts], fname
+        ret = "int" if restype is ctypes.c_int else "const char*"
+        calls.append(f"  {{ {ret} (*f)({', '.join(ctexts) or 'void'}) = {fname}; (void)f; }}")
+        zeros = [f"({c})0" if c.endswith("*") or c == "hipStream_t" else f"({c})z" for c in ctexts]      # z: no null pointer constant
+        calls.append(f"  (void){fname}({', '.join(zeros)});")
+    calls.append("}")
+    tu = tmp_path / "calls.c"
+    tu.write_text("\n".join(calls))
+    r = subprocess.run(cc + ["-Wall", "-Wextra", "-Werror", "-c", str(tu), "-o", str(tmp_path / "calls.o")], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
 
 
 def test_chain_launcher_validates_the_self_attention_arguments_without_gpu(lib):
