@@ -12,12 +12,14 @@ from .dataset import AIOZDataset, process_motion  # noqa: F401
 from .metrics import motion_metrics, beats_from_cond, evaluate_samples, summarize  # noqa: F401
 from .draw import camera, draw_dance, draw_samples, write_apng  # noqa: F401
 from .set_metrics import SetStats, kinetic_features, fit_reference, set_scores, evaluate_set, reference_from_joints  # noqa: F401
+from .set_metrics import GEOMETRIC_TABLE, geometric_features, geometric_table, evaluate_set_all  # noqa: F401
 from .music import music_features, assemble_cond, beat_track, music_cond, chroma_cqt, estimate_tuning, wav_cond  # noqa: F401
 from .audio import WavData, read_wav, decode, resample, slice_audio, load_audio  # noqa: F401
 
 __all__ = ["DanceDecoder", "GaussianDiffusion", "EMA", "Adan", "SMPLSkeleton", "ax_from_6v", "TrajDecoder", "TrajTrainer", "TrajAdamW",
            "traj_loss", "AIOZDataset", "process_motion", "motion_metrics", "beats_from_cond", "evaluate_samples", "summarize",
            "camera", "draw_dance", "draw_samples", "write_apng", "SetStats", "kinetic_features", "fit_reference", "set_scores",
-           "evaluate_set", "reference_from_joints", "music_features", "assemble_cond",
+           "evaluate_set", "reference_from_joints", "GEOMETRIC_TABLE", "geometric_features", "geometric_table", "evaluate_set_all",
+           "music_features", "assemble_cond",
            "beat_track", "music_cond", "chroma_cqt", "estimate_tuning", "wav_cond", "WavData", "read_wav", "decode", "resample",
            "slice_audio", "load_audio"]

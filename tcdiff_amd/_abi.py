@@ -1,6 +1,7 @@
 """The C ABI of libtcdiff_gfx950.so, read from include/tcdiff_hip.h: its integer macros, structs and prototypes as ctypes.
+include/tcdiff_hip_ext.h, the launchers added since the first header was pinned, is read the same way (load_ext).
 
-The header is the one place where the ABI is written down; _lib.py binds the library from what parse() returns.  The parser
+The headers are the one place where the ABI is written down; _lib.py binds the library from what parse() returns.  The parser
 knows the C that the header uses and nothing more, and it never guesses: a declaration it does not recognise raises
 TcdiffError with the header line.  Imports neither torch nor the library.
 """
@@ -10,6 +11,7 @@ import re
 from collections import namedtuple
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "tcdiff_hip.h")
+HEADER_EXT = os.path.join(os.path.dirname(HEADER), "tcdiff_hip_ext.h")
 
 
 class TcdiffError(RuntimeError):
@@ -131,3 +133,9 @@ def parse(text: str, name: str = "include/tcdiff_hip.h") -> Abi:
 def load() -> Abi:
     with open(HEADER) as f:
         return parse(f.read())
+
+
+def load_ext() -> Abi:
+    """the second header's own declarations; its #include of the first is a preprocessor line and is skipped"""
+    with open(HEADER_EXT) as f:
+        return parse(f.read(), "include/tcdiff_hip_ext.h")

@@ -1,4 +1,4 @@
-"""ctypes binding of libtcdiff_gfx950.so (include/tcdiff_hip.h).
+"""ctypes binding of libtcdiff_gfx950.so (include/tcdiff_hip.h and include/tcdiff_hip_ext.h).
 
 The product path has NO fallback: if the shared library is missing or a launcher returns an error, this
 module raises.  Nothing here touches ``oracle/``.
@@ -13,8 +13,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TCDIFF_LIB_PATH") or os.path.join(HERE, "libtcdiff_gfx950.so")   # override: diagnostic builds
 
 ABI = _abi.load()
+EXT = _abi.load_ext()                                # the second header: ABI stays the first header's
 
-for _name, _value in ABI.constants.items():          # TC_X -> X, TC_DTYPE_X -> DT_X
+for _name, _value in {**ABI.constants, **EXT.constants}.items():          # TC_X -> X, TC_DTYPE_X -> DT_X
     globals()["DT_" + _name[9:] if _name.startswith("TC_DTYPE_") else _name[3:]] = _value
 AUDIO_FMT = {f: ABI.constants["TC_AUDIO_" + f.upper()] for f in ("u8", "s16", "s24", "s32", "f32", "f64")}
 
@@ -32,7 +33,7 @@ AdanScalars = ABI.structs["tcdiff_adan_scalars"]
 NavAdamWScalars = ABI.structs["tcdiff_nav_adamw_scalars"]
 DrawStyle = ABI.structs["tcdiff_draw_style"]
 
-EXPORTS = sorted(ABI.functions)
+EXPORTS = sorted({**ABI.functions, **EXT.functions})
 
 _lib = None
 _rec = None          # a list while train_engine records a command list: every launcher call is appended as (function, arguments)
@@ -64,7 +65,7 @@ def load():
         raise TcdiffError(f"{LIB_PATH} not found: build it with `python -m tcdiff_amd.build` "
                           "(the MI355X path has no CPU fallback)")
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes, _) in ABI.functions.items():
+    for name, (restype, argtypes, _) in {**ABI.functions, **EXT.functions}.items():
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = argtypes, restype
     _lib = lib

@@ -574,6 +574,14 @@ def kinetic_features(joints, up, window, fps, feats):
             "tcdiff_kinetic_features")
 
 
+def geometric_features(joints, up, table, rng, time_per_frame, feats):
+    """joints (b, dn, T, 24, 3) fp32 view, read by its strides; table (R, 5) int32 and rng (R, 2) float64 contiguous on the device;
+    feats (b, dn, R) float64 contiguous"""
+    b, dn, T = joints.shape[:3]
+    L.check(L.load().tcdiff_geometric_features(_p(joints), _strides(joints, 3), b, dn, T, up, _p(table), _p(rng), table.shape[0],
+                                               time_per_frame, _p(feats), stream()), "tcdiff_geometric_features")
+
+
 def set_stats(feats, fit, mean, std, z, zc, mu, cov, div_rows):
     """feats (N, D) float64 contiguous; fit: mean / std are written, else read; z, zc (D, N) workspaces; div_rows (N,) or None"""
     N, D = feats.shape
