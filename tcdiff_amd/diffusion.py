@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import copy
 import os
+from functools import partial
 from typing import Callable, Optional
 
 import numpy as np
@@ -20,6 +21,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import kernels as K
+from .step_graphs import StepSpec, plan_runs, steps_per_graph
 
 
 def cosine_beta_schedule(n_timestep: int, cosine_s: float = 8e-3) -> np.ndarray:
@@ -126,6 +128,37 @@ class _LossFn(torch.autograd.Function):
 FOOT_JOINTS = [1, 2, 3, 4, 5, 7, 8, 10, 11]  # lower-body joints of ddim_sample_Footwork (model/diffusion.py:307)
 
 
+def sampler_steps(eng, st: dict, spec: StepSpec, u: int = 1):
+    """u sampler steps on the engine's sampler state `st`: the body of a captured step graph.  Which launches it issues, with which
+    arguments, comes from `spec` alone -- the graph's key -- so a graph cannot be replayed for a body it was not captured from."""
+    mode, branches, noise, traj, clip_offset, B, kind, q_noise, mask_rows, cparams, couple, form = spec
+    rows, nf = st["x"].shape
+    Lq = rows // B
+    for _ in range(u):
+        eng.step_prologue(st, 2 * B, st["x"], rows, form)
+        if branches == 2:
+            out = eng.network(st["x"], B, 2, 0, B, 0, x_ready=True, form=form)
+            unc, con = out, out[rows:]
+        else:
+            out = eng.network(st["x"], B, 1, 1, 0, B, x_ready=True, form=form)
+            unc, con = None, out
+        K.sampler_update(mode | L.SAMPLER_ADVANCE, unc, con, 152, st["x"], st["eps"] if noise else None,
+                         st["traj"] if traj else None, None, rows, nf, Lq, st["counter"], st["params"], st["tseq"], seed=0,
+                         clip0=clip_offset)
+        if kind is not None:
+            K.sampler_constrain(kind, st["x"], st["cmask"], mask_rows, st["cval"], st["qeps"] if q_noise else None, rows, nf, Lq,
+                                st["counter"], st["cparams"] if cparams else st["params"], st["tseq"], seed=0, clip0=clip_offset)
+        if couple is not None:
+            K.window_couple_step(st["x"], B, couple[0], couple[1], st["counter"], st["params"])
+
+
+def _capture(body: Callable[[], None]):
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        body()
+    return graph
+
+
 class GaussianDiffusion(nn.Module):
     def __init__(self, model, horizon, repr_dim, smpl, n_timestep=1000, schedule="linear", loss_type="l1",
                  clip_denoised=True, predict_epsilon=True, guidance_weight=3, use_p2=False, cond_drop_prob=0.2,
@@ -211,17 +244,7 @@ class GaussianDiffusion(nn.Module):
             eng.reset_graphs()
         return eng, rows
 
-    @staticmethod
-    def _steps_per_graph(run_len: int, unroll: int) -> int:
-        """steps per captured graph for a run of `run_len` equal steps: `unroll`, or -- when that leaves a tail of single-step replays
-        (50 DDIM steps = 20 + 20 + 10 x 1) -- the divisor of the run length nearest above / below it (50 -> 25)"""
-        if run_len < unroll or run_len % unroll == 0:
-            return unroll                       # (a run shorter than that goes step by step: a graph is captured on its SECOND visit,
-                                                # and a whole-run graph would be visited once per job)
-        for u in range(unroll + unroll // 2, unroll // 2, -1):
-            if run_len % u == 0:
-                return u
-        return unroll
+    _steps_per_graph = staticmethod(steps_per_graph)
 
     @staticmethod
     def _time_rows(tseq):
@@ -229,6 +252,37 @@ class GaussianDiffusion(nn.Module):
         uniq = sorted(set(int(t) for t in tseq))
         row_of = {t: i for i, t in enumerate(uniq)}
         return uniq, [row_of[int(t)] for t in tseq]
+
+    def _upload_job(self, eng, shape, x, tseq, params, traj, constrain, seed: int):
+        """The job's start and step tables into the engine's sampler state.  Returns (the state, the time-table row of every step, the
+        rows of the constraint's mask).
+        Host-to-device copies only, issued BEFORE the job's device work (_prepare: music branch, caches, tables): a copy from pageable
+        host memory blocks the host until everything queued before it has run, and behind _prepare's ~40 launches that was 0.6 ms of
+        host wait per job plus the launches that could not be queued meanwhile (a one-clip ddim_sample is 27 ms)."""
+        B, Lq, nf = shape
+        n = len(tseq)
+        rows = self._time_rows(tseq)[1]
+        st = eng.sampler_state(n, B * Lq, nf)
+        st["x"].copy_(x.reshape(B * Lq, nf))
+        st["counter"].zero_()
+        st["rows"][:n] = torch.tensor(rows, dtype=torch.int32)
+        st["tseq"][:n] = torch.tensor([int(t) for t in tseq], dtype=torch.int32)
+        st["params"][:n] = params.to(torch.float32)
+        # the constraint kernel's own step table (q_sample coefficients in columns 4, 5, enable bit in column 7): separate from the
+        # update kernel's, whose columns 4, 5 carry the predict_epsilon coefficients
+        if constrain is not None and constrain.get("params") is not None:
+            st["cparams"][:n] = constrain["params"].to(torch.float32)
+        if traj is not None:
+            st["traj"].copy_(traj.reshape(B * Lq, 3))
+        mask_rows = 0
+        if constrain is not None:
+            st["cval"].copy_(constrain["value"].reshape(B * Lq, nf))
+            m = constrain["mask"].to(st["x"].device, torch.float32).reshape(-1, nf)
+            mask_rows = Lq if m.shape[0] == Lq else B * Lq      # one [L, nfeat] mask for every clip, or a full one
+            st["cmask"][:mask_rows].copy_(m)
+        # the seed lives in device memory (counter[1..2]) so that a captured graph can be re-seeded
+        st["counter"][1:3] = torch.tensor([seed & 0x7FFFFFFF, (seed >> 31) & 0x7FFFFFFF], dtype=torch.int32)
+        return st, rows, mask_rows
 
     def _run(self, mode: int, shape, cond, x: torch.Tensor, tseq, params: torch.Tensor, *, traj=None,
              step_noise: Optional[Callable] = None, seed: Optional[int] = None, clip_offset: int = 0,
@@ -240,64 +294,15 @@ class GaussianDiffusion(nn.Module):
         (tcdiff_sampler_constrain / tcdiff_window_couple_step, enabled per step by params[:, 7] bits 1 / 0), so those
         samplers replay one graph per step like the plain ones; `after_step` remains for callers' own hooks."""
         B, Lq, nf = shape
-        n = len(tseq)
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        w_eff = params[:, 0].tolist()
-        x = x.reshape(B, Lq, nf)
+        branches = [1 if w == 1.0 else 2 for w in params[:, 0].tolist()]
         # one stream, one launch chain: with one resident-block kernel per layer the chip is full, and two half-batch chains on
         # two streams measured 3 % slower (rounds 1-3 kept that as a default-off option; removed in round 4)
-        # Host-to-device copies of the job's step tables FIRST, the job's device work (music branch, caches, tables) after them: a copy
-        # from pageable host memory blocks the host until everything queued before it has run, and behind _prepare's ~40 launches that
-        # was 0.6 ms of host wait per job plus the launches that could not be queued meanwhile (a one-clip ddim_sample is 27 ms).
         eng = self.model.engine(B, 0)
-        rows = self._time_rows(tseq)[1]
-        st = eng.sampler_state(n, B * Lq, nf)
-        st["x"].copy_(x.reshape(B * Lq, nf))
-        st["counter"].zero_()
-        st["rows"][:n] = torch.tensor(rows, dtype=torch.int32)
-        st["tseq"][:n] = torch.tensor([int(t) for t in tseq], dtype=torch.int32)
-        st["params"][:n] = params.to(torch.float32)
-        # the constraint kernel's own step table (q_sample coefficients in columns 4, 5, enable bit in column 7): separate from the
-        # update kernel's, whose columns 4, 5 carry the predict_epsilon coefficients
-        cpar = st["params"]
-        if constrain is not None and constrain.get("params") is not None:
-            st["cparams"][:n] = constrain["params"].to(torch.float32)
-            cpar = st["cparams"]
-        if traj is not None:
-            st["traj"].copy_(traj.reshape(B * Lq, 3))
-        mask_rows = 0
-        if constrain is not None:
-            st["cval"].copy_(constrain["value"].reshape(B * Lq, nf))
-            m = constrain["mask"].to(st["x"].device, torch.float32).reshape(-1, nf)
-            mask_rows = Lq if m.shape[0] == Lq else B * Lq      # one [L, nfeat] mask for every clip, or a full one
-            st["cmask"][:mask_rows].copy_(m)
-        # the seed lives in device memory (counter[1..2]) so that a captured graph can be re-seeded
-        st["counter"][1:3] = torch.tensor([seed & 0x7FFFFFFF, (seed >> 31) & 0x7FFFFFFF], dtype=torch.int32)
-        rows2 = self._prepare(B, cond, tseq, slot=0, eng=eng)[1]
-        assert rows2 == rows
-
-        def step(branches: int, form):
-            eng.step_prologue(st, 2 * B, st["x"], B * Lq, form)
-            if branches == 2:
-                out = eng.network(st["x"], B, 2, 0, B, 0, x_ready=True, form=form)
-                unc, con = out, out[B * Lq:]
-            else:
-                out = eng.network(st["x"], B, 1, 1, 0, B, x_ready=True, form=form)
-                unc, con = None, out
-            K.sampler_update(mode | L.SAMPLER_ADVANCE, unc, con, 152, st["x"], st["eps"] if step_noise is not None else None,
-                             st["traj"] if traj is not None else None, None, B * Lq, nf, Lq, st["counter"],
-                             st["params"], st["tseq"], seed=0, clip0=clip_offset)
-            if constrain is not None:
-                K.sampler_constrain(constrain["kind"], st["x"], st["cmask"], mask_rows, st["cval"],
-                                    st["qeps"] if constrain.get("q_noise") is not None else None, B * Lq, nf, Lq,
-                                    st["counter"], cpar, st["tseq"], seed=0, clip0=clip_offset)
-            if couple is not None:
-                K.window_couple_step(st["x"], B, couple[0], couple[1], st["counter"], st["params"])
-
-        graphs = self.__dict__.setdefault("_graphs", {})
-        is_step_key = lambda k: isinstance(k, tuple) and len(k) > 2 and k[0] != "warm"    # (the warm-up marks are ("warm", key))
-        gen = eng.generation
+        st, rows, mask_rows = self._upload_job(eng, shape, x, tseq, params, traj, constrain, seed)
+        assert self._prepare(B, cond, tseq, slot=0, eng=eng)[1] == rows
+        graphs = eng.step_graphs                # (fetched after _prepare, which drops them when a table moved)
         q_noise = constrain.get("q_noise") if constrain is not None else None
         # Every per-step quantity lives in device memory (counter, step tables, seed), so one captured graph serves every step -- and
         # SEVERAL consecutive steps of the same kind can be one graph: a replay boundary costs ~8 us of GPU idle time
@@ -305,53 +310,25 @@ class GaussianDiffusion(nn.Module):
         # between them (injected noise, callbacks, collected states) replay a graph of that many steps; the rest go one by one.
         hostless = step_noise is None and q_noise is None and after_step is None and collect is None
         unroll = max(1, int(os.environ.get("TCDIFF_GRAPH_STEPS", "20"))) if (use_graph and hostless) else 1
-        i = 0
-        run_until, run_u = 0, 1
-        while i < n:
-            t = tseq[i]
-            branches = 1 if w_eff[i] == 1.0 else 2
-            if unroll > 1 and i >= run_until:   # a new run of steps with the same branch count: its length picks the steps per graph
-                j = i
-                while j < n and (1 if w_eff[j] == 1.0 else 2) == branches:
-                    j += 1
-                run_until, run_u = j, self._steps_per_graph(j - i, unroll)
-            # (what is left of a run after its whole graphs goes one step at a time: no graph per tail length)
-            u = run_u if (unroll > 1 and i + run_u <= run_until) else 1
+        for i, u in plan_runs(branches, unroll):
+            t = int(tseq[i])
             if step_noise is not None:
-                st["eps"].copy_(step_noise(int(t), (B, Lq, nf)).reshape(B * Lq, nf))
+                st["eps"].copy_(step_noise(t, (B, Lq, nf)).reshape(B * Lq, nf))
             if q_noise is not None:
-                st["qeps"].copy_(q_noise(int(t), (B, Lq, nf)).reshape(B * Lq, nf))
-            # (the constraint kernel is captured reading st["cparams"] or st["params"]: part of the key -- ADVICE r5)
-            ckey = None if constrain is None else (constrain["kind"], q_noise is not None, mask_rows, constrain.get("params") is not None)
-            # (the kernel form the engine resolves from its switches for every forward -- small-job layers, parts 1 + 2 merged, the
-            # fragment front, the forked prologue -- is part of the key too: a switch changed after a capture must not replay the old
-            # form.  The launches below take the SAME value, so key and launches cannot disagree.)
-            form = eng.form(branches * B)
-            gkey = (mode, branches, step_noise is not None, traj is not None, clip_offset, B, gen, id(self.model), ckey, couple, u, form)
-            if not use_graph:
-                step(branches, form)
-            elif gkey in graphs:
-                graphs[gkey].replay()
-            elif ("warm", gkey) not in graphs:
-                for _ in range(u):
-                    step(branches, form)        # first visit: eager (loads code objects, sets kernel attributes)
-                graphs[("warm", gkey)] = True
-            else:                               # second visit: capture once, replay from now on
-                for k in [k for k in graphs if is_step_key(k) and k[7] == id(self.model) and k[6] != gen]:
-                    del graphs[k]               # graphs of engines whose buffers have moved
-                live = [k for k in graphs if is_step_key(k)]
-                for k in live[:max(0, len(live) - 15)]:
-                    del graphs[k]               # a bounded cache: at most 16 captured step graphs (oldest first) ...
-                    graphs.pop(("warm", k), None)   # ... and their warm-up marks
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
-                    for _ in range(u):
-                        step(branches, form)
-                graphs[gkey] = graph
-                graph.replay()
-            i += u
+                st["qeps"].copy_(q_noise(t, (B, Lq, nf)).reshape(B * Lq, nf))
+            # (the form is resolved from the engine's switches as they are now: a switch changed after a capture is another key)
+            spec = StepSpec(mode=mode, branches=branches[i], noise=step_noise is not None, traj=traj is not None,
+                            clip_offset=clip_offset, B=B, kind=None if constrain is None else constrain["kind"],
+                            q_noise=q_noise is not None, mask_rows=mask_rows,
+                            cparams=constrain is not None and constrain.get("params") is not None, couple=couple,
+                            form=eng.form(branches[i] * B))
+            body = partial(sampler_steps, eng, st, spec, u)
+            if use_graph:
+                graphs.visit((spec, u), body, _capture)
+            else:
+                body()
             if after_step is not None:
-                after_step(i - 1, int(t), st["x"].view(B, Lq, nf))
+                after_step(i + u - 1, t, st["x"].view(B, Lq, nf))
             if collect is not None:
                 collect.append(st["x"].view(B, Lq, nf).clone())
         return st["x"].view(B, Lq, nf).clone()

@@ -28,6 +28,7 @@ import torch
 from . import _lib as L
 from . import kernels as K
 from .form import Form, resolve_form
+from .step_graphs import StepGraphs
 
 NL_FILM = 3
 
@@ -91,13 +92,11 @@ class DenoiserEngine:
         self.chain_nw = int(os.environ.get("TCDIFF_CHAIN_NW", "8"))      # waves per workgroup of the chain launches (8 or 4)
         if self.chain_nw not in (4, 8):
             raise L.TcdiffError("TCDIFF_CHAIN_NW must be 8 or 4")
-        self.reset_graphs()
+        self.step_graphs = StepGraphs()            # the sampler's captured steps over THIS engine's buffers (diffusion.py _run)
 
     def reset_graphs(self):
         """Captured step graphs hold raw device pointers: drop them whenever any buffer may have moved."""
-        self.graphs = {}
-        self.graph_warm = set()
-        self.generation = getattr(self, "generation", 0) + 1
+        self.step_graphs.clear()
 
     def sampler_state(self, n_steps: int, rows: int, nfeat: int):
         """Persistent device-side sampler state (addresses are baked into captured graphs)."""

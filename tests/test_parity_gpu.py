@@ -911,3 +911,34 @@ def test_a_switch_changed_between_calls_takes_effect_in_captured_graphs(monkeypa
         print(f"{name}: shared object vs fresh object max-abs {float((got[name] - want[name]).abs().max()):.3e}")
     for name, _ in settings:
         assert torch.equal(got[name], want[name]), name
+
+
+def test_a_compute_dtype_changed_and_changed_back_starts_from_an_empty_graph_cache(monkeypatch):
+    """One diffusion object, bf16 -> f32 -> bf16: set_compute_dtype drops the engine, and the captured step graphs, which hold the
+    addresses of that engine's buffers, go with it (DenoiserEngine.step_graphs).  The third engine starts with no graph and its
+    sample equals, bit for bit, a fresh object's first call.  T = 100, 40 steps: 30 two-branch steps in graphs of 5 (TCDIFF_GRAPH_STEPS),
+    so the key is visited six times -- eager, capture, replay -- inside every call."""
+    monkeypatch.setenv("TCDIFF_GRAPH_STEPS", "5")
+    cond = torch.stack([O.synth_cond(0, 60)])
+    xT = torch.stack([O.synth_xT(0, 120)])
+
+    def run(diff):
+        return diff.p_sample_loop((1, 120, 151), cond, noise=xT, start_point=40, seed=77)
+
+    _, model, diff = build(2, 60, 100, "bf16")
+    first = run(diff)
+    eng1 = model.engine(1)
+    assert len(eng1.step_graphs.graphs()) == 2           # 5 two-branch steps (six visits), 5 one-branch steps (t < 10: two visits)
+    model.set_compute_dtype("f32")
+    f32 = run(diff)
+    assert model.engine(1) is not eng1 and len(model.engine(1).step_graphs.graphs()) > 0
+    model.set_compute_dtype("bf16")
+    eng3 = model.engine(1)
+    assert eng3 is not eng1 and len(eng3.step_graphs) == 0
+    third = run(diff)
+    assert model.engine(1) is eng3 and len(eng3.step_graphs.graphs()) > 0
+    _, _, fresh = build(2, 60, 100, "bf16")
+    want = run(fresh)
+    assert torch.equal(first, want)
+    assert torch.equal(third, want)
+    assert not torch.equal(f32, want), "the two modes must compute distinguishable samples for this test to have power"
