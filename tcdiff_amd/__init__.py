@@ -14,6 +14,7 @@ from .draw import camera, draw_dance, draw_samples, write_apng  # noqa: F401
 from .set_metrics import SetStats, kinetic_features, fit_reference, set_scores, evaluate_set, reference_from_joints  # noqa: F401
 from .set_metrics import GEOMETRIC_TABLE, geometric_features, geometric_table, evaluate_set_all  # noqa: F401
 from .music import music_features, assemble_cond, beat_track, music_cond, chroma_cqt, estimate_tuning, wav_cond  # noqa: F401
+from .gltf import animation_block, build_glb, write_glb, write_glb_out, convert_fk_out  # noqa: F401
 from .audio import WavData, read_wav, decode, resample, slice_audio, load_audio  # noqa: F401
 
 __all__ = ["DanceDecoder", "GaussianDiffusion", "EMA", "Adan", "SMPLSkeleton", "ax_from_6v", "TrajDecoder", "TrajTrainer", "TrajAdamW",
@@ -22,4 +23,4 @@ __all__ = ["DanceDecoder", "GaussianDiffusion", "EMA", "Adan", "SMPLSkeleton", "
            "evaluate_set", "reference_from_joints", "GEOMETRIC_TABLE", "geometric_features", "geometric_table", "evaluate_set_all",
            "music_features", "assemble_cond",
            "beat_track", "music_cond", "chroma_cqt", "estimate_tuning", "wav_cond", "WavData", "read_wav", "decode", "resample",
-           "slice_audio", "load_audio"]
+           "slice_audio", "load_audio", "animation_block", "build_glb", "write_glb", "write_glb_out", "convert_fk_out"]

@@ -1,5 +1,6 @@
 """The C ABI of libtcdiff_gfx950.so, read from include/tcdiff_hip.h: its integer macros, structs and prototypes as ctypes.
-include/tcdiff_hip_ext.h, the launchers added since the first header was pinned, is read the same way (load_ext).
+include/tcdiff_hip_ext.h, the launchers added since the first header was pinned, is read the same way (load_ext), and so is
+include/tcdiff_gltf.h, whose function carries the prefix tcx_ (load_gltf).
 
 The headers are the one place where the ABI is written down; _lib.py binds the library from what parse() returns.  The parser
 knows the C that the header uses and nothing more, and it never guesses: a declaration it does not recognise raises
@@ -12,6 +13,7 @@ from collections import namedtuple
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "tcdiff_hip.h")
 HEADER_EXT = os.path.join(os.path.dirname(HEADER), "tcdiff_hip_ext.h")
+HEADER_GLTF = os.path.join(os.path.dirname(HEADER), "tcdiff_gltf.h")
 
 
 class TcdiffError(RuntimeError):
@@ -29,7 +31,7 @@ _PREPROCESSOR = re.compile(r"^[ \t]*#[^\n]*", re.M)
 _DEFINE = re.compile(r"[ \t]*#[ \t]*define[ \t]+(\w+)(\(?)(.*)")
 _DECLARATOR = re.compile(r"\s*(\**)\s*(\w*)\s*((?:\[\s*\w*\s*\]\s*)*)")
 _STRUCT = re.compile(r"\s*typedef\s+struct\s*\w*\s*\{(.*)\}\s*(\w+)\s*", re.S)
-_FUNCTION = re.compile(r"\s*(int|const\s+char\s*\*)\s*(tcdiff_\w+)\s*\((.*)\)\s*", re.S)
+_FUNCTION = r"\s*(int|const\s+char\s*\*)\s*(%s\w+)\s*\((.*)\)\s*"          # % the functions' prefix
 _STREAM = re.compile(r"\s*typedef\s+struct\s+\w+\s*\*\s*hipStream_t\s*")
 
 
@@ -38,7 +40,9 @@ def _blank(m):
     return " " + "\n" * m.group().count("\n")
 
 
-def parse(text: str, name: str = "include/tcdiff_hip.h") -> Abi:
+def parse(text: str, name: str = "include/tcdiff_hip.h", prefix: str = "tcdiff_") -> Abi:
+    """``prefix``: what a function's name must start with; a prototype of another name is an unknown declaration"""
+    a_function = re.compile(_FUNCTION % re.escape(prefix), re.S)
     text = re.sub(r"/\*.*?\*/|//[^\n]*", _blank, text, flags=re.S)
     constants, structs, functions = {}, {}, {}
     types = dict(SCALARS, void=None)          # C type -> ctypes type; the structs join as they are declared
@@ -118,7 +122,7 @@ def parse(text: str, name: str = "include/tcdiff_hip.h") -> Abi:
                 fail(m.start(), "unbalanced braces", text[start:m.end()])
         elif depth == 0:
             decl, pos, start = text[start:m.start()], start, m.end()
-            s, f = _STRUCT.fullmatch(decl), _FUNCTION.fullmatch(decl)
+            s, f = _STRUCT.fullmatch(decl), a_function.fullmatch(decl)
             if s:
                 struct(s.group(1), s.group(2), pos + s.start(1))
             elif f:
@@ -139,3 +143,9 @@ def load_ext() -> Abi:
     """the second header's own declarations; its #include of the first is a preprocessor line and is skipped"""
     with open(HEADER_EXT) as f:
         return parse(f.read(), "include/tcdiff_hip_ext.h")
+
+
+def load_gltf() -> Abi:
+    """the third header: one launcher, named tcx_* because the set of tcdiff_* symbols is frozen (the header says why)"""
+    with open(HEADER_GLTF) as f:
+        return parse(f.read(), "include/tcdiff_gltf.h", prefix="tcx_")

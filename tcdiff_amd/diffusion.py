@@ -693,7 +693,8 @@ class GaussianDiffusion(nn.Module):
     @torch.no_grad()
     def render_sample(self, shape, cond, normalizer=None, epoch=None, render_out=None, fk_out=None, name=None,
                       sound=True, mode="normal", noise=None, constraint=None, sound_folder="ood_sliced",
-                      start_point=None, render=True, required_dancer_num=4, x_0=None, render_len=512, *, draw_out=None):
+                      start_point=None, render=True, required_dancer_num=4, x_0=None, render_len=512, *, glb_out=None,
+                      draw_out=None):
         """Mode dispatch of the reference (model/diffusion.py:784-806); a tensor ``shape`` is taken as the samples.
 
         With a ``normalizer`` and an ``fk_out`` directory, the post-processing of model/diffusion.py:811-988 follows:
@@ -707,15 +708,23 @@ class GaussianDiffusion(nn.Module):
         rasteriser instead of matplotlib) and written as animated PNGs, clip by clip: ``e{epoch}_b{num}_{clip}.png`` per clip,
         or ``{epoch}_{song}.png`` of the song's first ``render_len`` frames in "long" mode -- the reference's names with the new
         extension.  No audio is muxed.  ``render_out``, ``sound``, ``sound_folder`` and ``render`` are unused: without
-        ``draw_out`` nothing is drawn.  The samples are returned either way (the reference returns None)."""
+        ``draw_out`` nothing is drawn.
+
+        With a ``normalizer`` and a ``glb_out`` directory (keyword only), the exported poses are also written as animated glTF
+        files (tcdiff_amd/gltf.py: the open counterpart of the reference's Blender_Visulization/ FBX conversion), one per clip with
+        all its dancers, under ``fk_out``'s names with the extension .glb.  The export runs once whichever of the three asks.
+        The samples are returned either way (the reference returns None)."""
         samples = self._render_samples(shape, cond, mode, noise, constraint, start_point, x_0)
-        if normalizer is not None and (fk_out is not None or draw_out is not None):
+        if normalizer is not None and (fk_out is not None or draw_out is not None or glb_out is not None):
             from .export import export_poses, write_fk_out
             x = samples if samples.is_cuda else samples.to(self._device())
             parents, offsets = self._skeleton(x.device)
             q, pos, poses, contacts = export_poses(x, normalizer, mode, required_dancer_num, parents=parents, offsets=offsets)
             if fk_out is not None:
                 write_fk_out(fk_out, mode, epoch, name, q, pos, poses)
+            if glb_out is not None:
+                from .gltf import write_glb_out
+                write_glb_out(glb_out, mode, epoch, name, q, pos, required_dancer_num, parents=parents, offsets=offsets)
             if draw_out is not None:
                 from .draw import write_draw_out
                 write_draw_out(draw_out, mode, epoch, name, poses, contacts, render_len=render_len, parents=parents)

@@ -549,6 +549,11 @@ def pose_export(samples, b, S, dn, mode, scale, min_, fade, parents, offsets, sm
                                         _p(smpl_poses), _p(full_pose), _p(contact), stream()), "tcdiff_pose_export")
 
 
+def gltf_animation(smpl_poses, smpl_trans, clips, T, dn, fps, out):
+    """smpl_poses (clips, T, dn, 24, 3) / smpl_trans (clips, T, dn, 3) fp32 contiguous; out (clips, T (1 + 99 dn)) fp32 contiguous"""
+    L.check(L.load().tcx_gltf_animation(_p(smpl_poses), _p(smpl_trans), clips, T, dn, fps, _p(out), stream()), "tcx_gltf_animation")
+
+
 # ---- motion ingest -------------------------------------------------------------------------------------------------------
 def motion_ingest(pos, q, clips, dn, sq, parents, offsets, fit, scale, min_, feats, raw, feet, stats):
     L.check(L.load().tcdiff_motion_ingest(_p(pos), _p(q), clips, dn, sq, *_skeleton(parents, offsets), int(bool(fit)), _p(scale), _p(min_), _p(feats),
