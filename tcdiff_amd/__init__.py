@@ -15,6 +15,7 @@ from .set_metrics import SetStats, kinetic_features, fit_reference, set_scores, 
 from .set_metrics import GEOMETRIC_TABLE, geometric_features, geometric_table, evaluate_set_all  # noqa: F401
 from .music import music_features, assemble_cond, beat_track, music_cond, chroma_cqt, estimate_tuning, wav_cond  # noqa: F401
 from .gltf import animation_block, build_glb, write_glb, write_glb_out, convert_fk_out  # noqa: F401
+from .body import BodyModel, load_body_model, skin  # noqa: F401
 from .audio import WavData, read_wav, decode, resample, slice_audio, load_audio  # noqa: F401
 
 __all__ = ["DanceDecoder", "GaussianDiffusion", "EMA", "Adan", "SMPLSkeleton", "ax_from_6v", "TrajDecoder", "TrajTrainer", "TrajAdamW",
@@ -23,4 +24,5 @@ __all__ = ["DanceDecoder", "GaussianDiffusion", "EMA", "Adan", "SMPLSkeleton", "
            "evaluate_set", "reference_from_joints", "GEOMETRIC_TABLE", "geometric_features", "geometric_table", "evaluate_set_all",
            "music_features", "assemble_cond",
            "beat_track", "music_cond", "chroma_cqt", "estimate_tuning", "wav_cond", "WavData", "read_wav", "decode", "resample",
-           "slice_audio", "load_audio", "animation_block", "build_glb", "write_glb", "write_glb_out", "convert_fk_out"]
+           "slice_audio", "load_audio", "animation_block", "build_glb", "write_glb", "write_glb_out", "convert_fk_out",
+           "BodyModel", "load_body_model", "skin"]

@@ -1,6 +1,6 @@
 """The C ABI of libtcdiff_gfx950.so, read from include/tcdiff_hip.h: its integer macros, structs and prototypes as ctypes.
 include/tcdiff_hip_ext.h, the launchers added since the first header was pinned, is read the same way (load_ext), and so is
-include/tcdiff_gltf.h, whose function carries the prefix tcx_ (load_gltf).
+include/tcdiff_gltf.h, whose function carries the prefix tcx_ (load_gltf), and include/tcdiff_skin.h, prefix tcs_ (load_skin).
 
 The headers are the one place where the ABI is written down; _lib.py binds the library from what parse() returns.  The parser
 knows the C that the header uses and nothing more, and it never guesses: a declaration it does not recognise raises
@@ -14,6 +14,7 @@ from collections import namedtuple
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "tcdiff_hip.h")
 HEADER_EXT = os.path.join(os.path.dirname(HEADER), "tcdiff_hip_ext.h")
 HEADER_GLTF = os.path.join(os.path.dirname(HEADER), "tcdiff_gltf.h")
+HEADER_SKIN = os.path.join(os.path.dirname(HEADER), "tcdiff_skin.h")
 
 
 class TcdiffError(RuntimeError):
@@ -149,3 +150,9 @@ def load_gltf() -> Abi:
     """the third header: one launcher, named tcx_* because the set of tcdiff_* symbols is frozen (the header says why)"""
     with open(HEADER_GLTF) as f:
         return parse(f.read(), "include/tcdiff_gltf.h", prefix="tcx_")
+
+
+def load_skin() -> Abi:
+    """the fourth header: one launcher, tcs_skin_vertices, and its tile sizes as constants; tcs_* because tcdiff_* and tcx_* are frozen"""
+    with open(HEADER_SKIN) as f:
+        return parse(f.read(), "include/tcdiff_skin.h", prefix="tcs_")

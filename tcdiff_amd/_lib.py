@@ -1,4 +1,4 @@
-"""ctypes binding of libtcdiff_gfx950.so (include/tcdiff_hip.h, include/tcdiff_hip_ext.h and include/tcdiff_gltf.h).
+"""ctypes binding of libtcdiff_gfx950.so (include/tcdiff_hip.h, include/tcdiff_hip_ext.h, include/tcdiff_gltf.h and include/tcdiff_skin.h).
 
 The product path has NO fallback: if the shared library is missing or a launcher returns an error, this
 module raises.  Nothing here touches ``oracle/``.
@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("TCDIFF_LIB_PATH") or os.path.join(HERE, "libtcdiff_gf
 ABI = _abi.load()
 EXT = _abi.load_ext()                                # the second header: ABI stays the first header's
 GLTF = _abi.load_gltf()                              # the third: tcx_gltf_animation, bound below, in none of ABI, EXT, EXPORTS
+SKIN = _abi.load_skin()                              # the fourth: tcs_skin_vertices and its tile sizes, bound below, in none of the others
 
 for _name, _value in {**ABI.constants, **EXT.constants}.items():          # TC_X -> X, TC_DTYPE_X -> DT_X
     globals()["DT_" + _name[9:] if _name.startswith("TC_DTYPE_") else _name[3:]] = _value
@@ -66,7 +67,7 @@ def load():
         raise TcdiffError(f"{LIB_PATH} not found: build it with `python -m tcdiff_amd.build` "
                           "(the MI355X path has no CPU fallback)")
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes, _) in {**ABI.functions, **EXT.functions, **GLTF.functions}.items():
+    for name, (restype, argtypes, _) in {**ABI.functions, **EXT.functions, **GLTF.functions, **SKIN.functions}.items():
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = argtypes, restype
     _lib = lib

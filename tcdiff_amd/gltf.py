@@ -9,8 +9,10 @@ The numbers of a file -- key-frame times, the root's translation and rotation tu
 local rotation as a quaternion whose sign is continuous in time -- are made on the device in one launch (``tcx_gltf_animation``,
 csrc/gltf.hip; defined in include/tcdiff_gltf.h) as one block per clip, and that block IS the head of the file's binary chunk:
 ``build_glb`` only writes the JSON that points into it and appends the static data (a stick body of one octahedron per bone,
-rigidly skinned).  Not built: the SMPL body mesh (its skinning weights are not ours to ship), FBX, audio (glTF has none),
-key-frame reduction, cameras and lights.  Parity with the Khronos validator and with Blender's importer is unpinned: neither is
+rigidly skinned -- or, with ``mesh=`` a ``BodyModel`` (tcdiff_amd/body.py: the user's own SMPL model file, none is shipped), the
+model's surface as a skinned mesh).  Not built: shipping a model, FBX, per-frame normals, the pose-corrective blend shapes inside
+the file and more than four weights per vertex (core glTF has neither), one body shape per dancer, audio (glTF has none), key-frame
+reduction, cameras and lights.  Parity with the Khronos validator and with Blender's importer is unpinned: neither is
 a dependency, conformance rests on the glTF 2.0 specification as the tests' reader restates it.
 """
 from __future__ import annotations
@@ -39,7 +41,7 @@ BONE_RADIUS = 0.12            # the octahedron's half-width as a fraction of the
 BONE_RADIUS_MAX = 0.03        # ... capped, in metres
 BONE_WAIST = 0.2              # where along the bone its widest ring sits
 
-_FLOAT, _UBYTE, _USHORT = 5126, 5121, 5123            # glTF componentType
+_FLOAT, _UBYTE, _USHORT, _UINT = 5126, 5121, 5123, 5125     # glTF componentType
 _ARRAY_BUFFER, _ELEMENT_ARRAY_BUFFER = 34962, 34963   # glTF bufferView.target
 
 
@@ -143,7 +145,31 @@ def _bones(parents, rest):
             np.arange(V, dtype=np.uint16))
 
 
-def build_glb(block, T, dn, fps, *, parents=None, offsets=None, colors=PALETTE, body=True) -> bytes:
+def _surface(mesh):
+    """A ``BodyModel``'s surface as glTF vertex data: (positions = v_shaped (V, 3) f32, the rest normals (V, 3) f32, joints (V, 4)
+    u8, weights (V, 4) f32, indices (3F,) u16 or, above 65 535 vertices, u32).  Normals: the faces' area-weighted normals (the
+    cross products as they are) summed per vertex in float64 and normalised; a vertex whose sum is zero gets (0, 1, 0).  Joints and
+    weights: each vertex's four largest weights, ties to the lower joint, renormalised to sum to 1 in float64."""
+    V, faces = mesh.V, mesh.faces
+    p = mesh.v_shaped
+    n = np.zeros((V, 3), np.float64)
+    fn = np.cross(p[faces[:, 1]] - p[faces[:, 0]], p[faces[:, 2]] - p[faces[:, 0]])
+    for c in range(3):
+        np.add.at(n, faces[:, c], fn)
+    length = np.sqrt((n * n).sum(1))
+    flat = ~(length > 0)
+    n[~flat] /= length[~flat, None]
+    n[flat] = (0.0, 1.0, 0.0)
+    w = mesh.weights
+    top = np.argsort(-w, axis=1, kind="stable")[:, :4]                    # stable: among equal weights the lower joint first
+    wt = np.take_along_axis(w, top, 1)
+    wt = wt / wt.sum(1, keepdims=True)
+    top = np.where(wt != 0, top, 0)
+    return (p.astype(np.float32), n.astype(np.float32), top.astype(np.uint8), wt.astype(np.float32),
+            faces.reshape(-1).astype(np.uint16 if V <= 65535 else np.uint32))
+
+
+def build_glb(block, T, dn, fps, *, parents=None, offsets=None, colors=PALETTE, body=True, mesh=None) -> bytes:
     """One clip's block (F = T (1 + 99 dn) float32, a numpy array as ``animation_block(...)[i].cpu().numpy()`` gives it) -> the
     bytes of a .glb file.  Pure host code: the 12-byte header, a JSON chunk, one BIN chunk that is the block as it is followed by
     the static data.
@@ -152,8 +178,24 @@ def build_glb(block, T, dn, fps, *, parents=None, offsets=None, colors=PALETTE, 
     ``offsets[j]`` (joint 0 has none: its translation is animated); one animation with, per dancer, a ``translation`` channel on
     joint 0 and 24 ``rotation`` channels, LINEAR, all on one time accessor whose min / max are read from the block.  ``body``:
     a skin per dancer and a mesh of one octahedron per bone in the dancer's colour (``colors[d % n]``, sRGB 0..255) -- without
-    it a viewer has nothing to shade, only the armature.  ``fps`` is what the block was made with; it names the animation."""
+    it a viewer has nothing to shade, only the armature.  ``fps`` is what the block was made with; it names the animation.
+
+    ``mesh``: a ``BodyModel`` (``load_body_model``).  The dancers' meshes are then the model's surface instead of the octahedra:
+    POSITION ``v_shaped``, NORMAL the rest normals, JOINTS_0 / WEIGHTS_0 each vertex's four largest weights renormalised, inverse
+    bind matrices that translate by -J_j, and the skeleton is the MODEL's (its parents, its offsets as the nodes' translations):
+    an explicit ``parents`` or ``offsets`` beside ``mesh`` raises, the body would bind at one skeleton and move on another.  The
+    file's vertices are ``skin(..., pose_blend=False, origin="pelvis")`` turned to Y-up, with the four kept weights: the
+    pose-corrective blend shapes and weights beyond four cannot be expressed in core glTF."""
     T, dn = int(T), int(dn)
+    if mesh is not None:
+        if parents is not None or offsets is not None:
+            raise L.TcdiffError("build_glb: mesh= brings the model's own skeleton; parents= or offsets= beside it would move the body on "
+                                "a skeleton it is not bound to")
+        if not body:
+            raise L.TcdiffError("build_glb: mesh= beside body=False")
+        if not all(hasattr(mesh, k) for k in ("v_shaped", "faces", "weights", "J", "offsets", "parents")):
+            raise L.TcdiffError("build_glb: mesh must be what load_body_model returns")
+        parents, offsets = mesh.parents, mesh.offsets
     parents = [int(p) for p in (SMPL_PARENTS if parents is None else parents)]
     offsets = np.asarray(SMPL_OFFSETS if offsets is None else offsets, np.float64)
     if T < 1 or dn < 1:
@@ -209,10 +251,13 @@ def build_glb(block, T, dn, fps, *, parents=None, offsets=None, colors=PALETTE, 
             channels.append({"sampler": len(samplers) - 1, "target": {"node": 24 * d + j, "path": "rotation"}})
     gltf = {"asset": {"version": "2.0", "generator": "tcdiff_amd"}, "scene": 0}
 
-    pos, nrm, jnt, wgt, idx = _bones(parents, rest) if body else (np.zeros((0, 3), np.float32),) * 5
+    if mesh is not None:
+        pos, nrm, jnt, wgt, idx = _surface(mesh)
+    else:
+        pos, nrm, jnt, wgt, idx = _bones(parents, rest) if body else (np.zeros((0, 3), np.float32),) * 5
     if len(pos):
         ibm = np.tile(np.eye(4, dtype=np.float32).reshape(1, 16), (24, 1))             # column-major: the translation is 12 .. 14
-        ibm[:, 12:15] = -rest
+        ibm[:, 12:15] = -rest if mesh is None else -mesh.J          # POSITION is in the model's frame: the pelvis at J_0
         a_ibm = accessor(view(ibm.astype("<f4").tobytes()), 0, _FLOAT, 24, "MAT4")
         attributes = {
             "POSITION": accessor(view(pos.astype("<f4").tobytes(), _ARRAY_BUFFER), 0, _FLOAT, len(pos), "VEC3",
@@ -220,7 +265,9 @@ def build_glb(block, T, dn, fps, *, parents=None, offsets=None, colors=PALETTE, 
             "NORMAL": accessor(view(nrm.astype("<f4").tobytes(), _ARRAY_BUFFER), 0, _FLOAT, len(pos), "VEC3"),
             "JOINTS_0": accessor(view(jnt.tobytes(), _ARRAY_BUFFER), 0, _UBYTE, len(pos), "VEC4"),
             "WEIGHTS_0": accessor(view(wgt.astype("<f4").tobytes(), _ARRAY_BUFFER), 0, _FLOAT, len(pos), "VEC4")}
-        a_idx = accessor(view(idx.astype("<u2").tobytes(), _ELEMENT_ARRAY_BUFFER), 0, _USHORT, len(idx), "SCALAR")
+        wide = idx.dtype == np.uint32
+        a_idx = accessor(view(idx.astype("<u4" if wide else "<u2").tobytes(), _ELEMENT_ARRAY_BUFFER), 0, _UINT if wide else _USHORT,
+                         len(idx), "SCALAR")
         colors = np.asarray(colors, np.float64)
         if colors.ndim != 2 or colors.shape[0] < 1 or colors.shape[1] != 3 or (colors < 0).any() or (colors > 255).any():
             raise L.TcdiffError("build_glb: colors must be (n >= 1, 3) values in 0..255")
@@ -229,8 +276,8 @@ def build_glb(block, T, dn, fps, *, parents=None, offsets=None, colors=PALETTE, 
             rgb = [_srgb_to_linear(v) for v in colors[d % len(colors)]]
             gltf["materials"].append({"name": f"d{d}", "pbrMetallicRoughness": {"baseColorFactor": rgb + [1.0], "metallicFactor": 0.0,
                                                                                  "roughnessFactor": 0.8}})
-            gltf["meshes"].append({"name": f"d{d}_bones", "primitives": [{"attributes": attributes, "indices": a_idx, "material": d,
-                                                                          "mode": 4}]})
+            gltf["meshes"].append({"name": f"d{d}_bones" if mesh is None else f"d{d}_surface",
+                                   "primitives": [{"attributes": attributes, "indices": a_idx, "material": d, "mode": 4}]})
             gltf["skins"].append({"name": f"d{d}", "joints": list(range(24 * d, 24 * d + 24)), "inverseBindMatrices": a_ibm,
                                   "skeleton": 24 * d})
             nodes.append({"name": f"d{d}_body", "mesh": d, "skin": d})
@@ -251,10 +298,12 @@ def build_glb(block, T, dn, fps, *, parents=None, offsets=None, colors=PALETTE, 
                      struct.pack("<I4s", len(binary), b"BIN\0"), binary])
 
 
-def write_glb(path, smpl_poses, smpl_trans, dn, *, fps=30.0, **kw) -> list:
+def write_glb(path, smpl_poses, smpl_trans, dn, *, fps=30.0, mesh=None, **kw) -> list:
     """``animation_block`` once for all clips, one device-to-host copy, then ``build_glb`` per clip.  ``path``: one path per clip
-    (fewer paths: only the first clips are written), or a single path for a single clip.  ``kw`` goes to ``build_glb``.  Returns
-    the paths written."""
+    (fewer paths: only the first clips are written), or a single path for a single clip.  ``mesh`` (a ``BodyModel``: the dancers'
+    surfaces instead of the stick bodies) and ``kw`` go to ``build_glb``.  Returns the paths written."""
+    if mesh is not None:
+        kw["mesh"] = mesh
     single = isinstance(path, (str, os.PathLike))
     paths = [path] if single else list(path)
     block = animation_block(smpl_poses, smpl_trans, dn, fps)
@@ -279,7 +328,7 @@ def glb_out_names(mode: str, epoch, name) -> list:
     return [os.path.splitext(n)[0] + ".glb" for n in fk_out_names(mode, epoch, name)]
 
 
-def write_glb_out(glb_out, mode: str, epoch, name, q, pos, dn, *, fps=30.0, **kw) -> list:
+def write_glb_out(glb_out, mode: str, epoch, name, q, pos, dn, *, fps=30.0, mesh=None, **kw) -> list:
     """Writes ``export_poses``' first two results as .glb files, one per clip with all its dancers (the first min(b, len(name))
     clips, as the reference's zip), or one per song in "long" mode.  Returns the paths written."""
     names = glb_out_names(mode, epoch, name)
@@ -287,10 +336,10 @@ def write_glb_out(glb_out, mode: str, epoch, name, q, pos, dn, *, fps=30.0, **kw
     n = 1 if _is_long(mode) else min(len(names), q.shape[0])
     if n < 1:
         return []
-    return write_glb([os.path.join(glb_out, f) for f in names[:n]], q[:n], pos[:n], dn, fps=fps, **kw)
+    return write_glb([os.path.join(glb_out, f) for f in names[:n]], q[:n], pos[:n], dn, fps=fps, mesh=mesh, **kw)
 
 
-def convert_fk_out(pkl_path, glb_path=None, fps=30.0, **kw) -> str:
+def convert_fk_out(pkl_path, glb_path=None, fps=30.0, mesh=None, **kw) -> str:
     """A pickle that ``write_fk_out`` (or the reference) wrote earlier -> a .glb file beside it (or at ``glb_path``): what the
     reference's 1-preProcess_group_smpl.py and 2-ConvertPkl2FBX_SMPL.py do together.  The number of dancers is
     ``full_pose.shape[0]``."""
@@ -308,4 +357,4 @@ def convert_fk_out(pkl_path, glb_path=None, fps=30.0, **kw) -> str:
     q = torch.from_numpy(np.ascontiguousarray(poses, np.float32)).to(dev)
     p = torch.from_numpy(np.ascontiguousarray(trans, np.float32)).to(dev)
     out = os.path.splitext(os.fspath(pkl_path))[0] + ".glb" if glb_path is None else os.fspath(glb_path)
-    return write_glb(out, q, p, dn, fps=fps, **kw)[0]
+    return write_glb(out, q, p, dn, fps=fps, mesh=mesh, **kw)[0]

@@ -554,6 +554,16 @@ def gltf_animation(smpl_poses, smpl_trans, clips, T, dn, fps, out):
     L.check(L.load().tcx_gltf_animation(_p(smpl_poses), _p(smpl_trans), clips, T, dn, fps, _p(out), stream()), "tcx_gltf_animation")
 
 
+def skin_vertices(smpl_poses, smpl_trans, P, v_shaped, blend, joints, offsets, parents, weights, weight_joints, V, Kw, pose_blend, origin,
+                  feat, A, joints_out, out):
+    """include/tcdiff_skin.h: smpl_poses (P, 24, 3) / smpl_trans (P, 3) fp32 contiguous; the model's device images; ``parents`` a
+    host ctypes array of 24 ints; feat (P, 208) and A (P, 24, 12) fp32 workspaces; joints_out (P, 24, 3) or None; out (P, V, 3)"""
+    L.check(L.load().tcs_skin_vertices(_p(smpl_poses), _p(smpl_trans), P, _p(v_shaped), _p(blend), _p(joints), _p(offsets),
+                                       C.cast(parents, C.c_void_p), _p(weights), _p(weight_joints), V, Kw, pose_blend, origin,
+                                       _p(feat), _p(A), _p(joints_out), _p(out), stream()),
+            "tcs_skin_vertices")
+
+
 # ---- motion ingest -------------------------------------------------------------------------------------------------------
 def motion_ingest(pos, q, clips, dn, sq, parents, offsets, fit, scale, min_, feats, raw, feet, stats):
     L.check(L.load().tcdiff_motion_ingest(_p(pos), _p(q), clips, dn, sq, *_skeleton(parents, offsets), int(bool(fit)), _p(scale), _p(min_), _p(feats),
