@@ -641,6 +641,16 @@ int tcdiff_row_param_reduce(const float* partials, int n_blocks, float* d_bias, 
  * delta_i = sum_d dO_id O_id is taken from O + O_lo (16 bits of O instead of 8).  Round 6 found why it matters: delta enters
  * dS = P (dP - delta), a cancellation, and 8-bit O alone put the decoder's self-attention w_qs / w_ks gradients at twice the error the
  * operand rounding of the step explains (tests/test_train_step_gpu.py, oracle._AttnKernelDelta). */
+/* Padding and workspaces of both calls (enforced bit for bit by tests/test_attn_train_f64_gpu.py):
+ *   - the pad rows of the Q', K and V images (rows Lq .. Lp_q - 1, Lk .. Lp_k - 1) may hold ANY FINITE values: every key past Lk is
+ *     masked by a select and no row past Lq is stored.  Not Inf or NaN: a masked weight of zero times Inf is NaN;
+ *   - the pad rows of the dO image must be ZERO (the only padding the backward requires to be zero);
+ *   - lse is written at [seq][head][0 .. Lq - 1] only; its pad slots are neither written nor used, whatever they hold;
+ *   - delta is a pure workspace: it needs no initialisation (NaN-filled is fine), is written at [0 .. Lq - 1] per (seq, head) before
+ *     it is read, and its pad slots are neither written nor used;
+ *   - O, O_lo, dQ, dK, dV are written at their Lq (Lk) rows x 64 H columns only: columns up to the leading dimension and rows
+ *     beyond the last sequence are left alone.
+ * Lp_q % 128 == 0; Lp_k % 64 == 0 for the forward, % 128 for the backward. */
 int tcdiff_attention_train(int dtype, const void* Q, const void* K, const void* V, void* O, void* O_lo, float* lse, int n_seq,
                            int H, int Lq, int Lk, int Lp_q, int Lp_k, int ldo, const int* seed, int site, uint32_t drop_thr,
                            float drop_scale, hipStream_t stream);
