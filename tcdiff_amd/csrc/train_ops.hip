@@ -223,6 +223,8 @@ __global__ __launch_bounds__(256) void act_drop_kernel(const S* __restrict__ a, 
         if (c < cols) {
             const bool keep = thr ? drop_keep(dc, (uint32_t)row * (uint32_t)cols + (uint32_t)c) : true;
             if (!BWD) r = keep ? apply_act(xa[j], act) * dscale : 0.0f;
+            // ReLU as a select, like the fused epilogue of gemm_tile_kernel (act_src): dy * 0 would leave -0 under a negative dy
+            else if (act == ACT_RELU) r = (keep && xa[j] > 0.0f) ? ga[j] * dscale : 0.0f;
             else r = keep ? ga[j] * dscale * act_grad(xa[j], act) : 0.0f;
         }
         v[j] = r;
