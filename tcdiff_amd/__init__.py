@@ -16,6 +16,7 @@ from .set_metrics import GEOMETRIC_TABLE, geometric_features, geometric_table, e
 from .music import music_features, assemble_cond, beat_track, music_cond, chroma_cqt, estimate_tuning, wav_cond  # noqa: F401
 from .gltf import animation_block, build_glb, write_glb, write_glb_out, convert_fk_out  # noqa: F401
 from .body import BodyModel, load_body_model, skin  # noqa: F401
+from .shade import vertex_normals, draw_bodies, draw_body_samples  # noqa: F401
 from .audio import WavData, read_wav, decode, resample, slice_audio, load_audio  # noqa: F401
 
 __all__ = ["DanceDecoder", "GaussianDiffusion", "EMA", "Adan", "SMPLSkeleton", "ax_from_6v", "TrajDecoder", "TrajTrainer", "TrajAdamW",
@@ -25,4 +26,4 @@ __all__ = ["DanceDecoder", "GaussianDiffusion", "EMA", "Adan", "SMPLSkeleton", "
            "music_features", "assemble_cond",
            "beat_track", "music_cond", "chroma_cqt", "estimate_tuning", "wav_cond", "WavData", "read_wav", "decode", "resample",
            "slice_audio", "load_audio", "animation_block", "build_glb", "write_glb", "write_glb_out", "convert_fk_out",
-           "BodyModel", "load_body_model", "skin"]
+           "BodyModel", "load_body_model", "skin", "vertex_normals", "draw_bodies", "draw_body_samples"]

@@ -1,6 +1,7 @@
 """The C ABI of libtcdiff_gfx950.so, read from include/tcdiff_hip.h: its integer macros, structs and prototypes as ctypes.
 include/tcdiff_hip_ext.h, the launchers added since the first header was pinned, is read the same way (load_ext), and so is
-include/tcdiff_gltf.h, whose function carries the prefix tcx_ (load_gltf), and include/tcdiff_skin.h, prefix tcs_ (load_skin).
+include/tcdiff_gltf.h, whose function carries the prefix tcx_ (load_gltf), include/tcdiff_skin.h, prefix tcs_ (load_skin), and include/tcdiff_shade.h,
+prefix tcr_ (load_shade).
 
 The headers are the one place where the ABI is written down; _lib.py binds the library from what parse() returns.  The parser
 knows the C that the header uses and nothing more, and it never guesses: a declaration it does not recognise raises
@@ -15,6 +16,7 @@ HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))
 HEADER_EXT = os.path.join(os.path.dirname(HEADER), "tcdiff_hip_ext.h")
 HEADER_GLTF = os.path.join(os.path.dirname(HEADER), "tcdiff_gltf.h")
 HEADER_SKIN = os.path.join(os.path.dirname(HEADER), "tcdiff_skin.h")
+HEADER_SHADE = os.path.join(os.path.dirname(HEADER), "tcdiff_shade.h")
 
 
 class TcdiffError(RuntimeError):
@@ -156,3 +158,10 @@ def load_skin() -> Abi:
     """the fourth header: one launcher, tcs_skin_vertices, and its tile sizes as constants; tcs_* because tcdiff_* and tcx_* are frozen"""
     with open(HEADER_SKIN) as f:
         return parse(f.read(), "include/tcdiff_skin.h", prefix="tcs_")
+
+
+def load_shade() -> Abi:
+    """the fifth header: the mesh rasteriser's two launchers, tcr_mesh_vertices and tcr_mesh_raster, its style struct and its tile
+    and chunk sizes as constants; tcr_* because tcdiff_*, tcx_* and tcs_* are frozen"""
+    with open(HEADER_SHADE) as f:
+        return parse(f.read(), "include/tcdiff_shade.h", prefix="tcr_")

@@ -1,4 +1,5 @@
-"""ctypes binding of libtcdiff_gfx950.so (include/tcdiff_hip.h, include/tcdiff_hip_ext.h, include/tcdiff_gltf.h and include/tcdiff_skin.h).
+"""ctypes binding of libtcdiff_gfx950.so (include/tcdiff_hip.h, include/tcdiff_hip_ext.h, include/tcdiff_gltf.h, include/tcdiff_skin.h
+and include/tcdiff_shade.h).
 
 The product path has NO fallback: if the shared library is missing or a launcher returns an error, this
 module raises.  Nothing here touches ``oracle/``.
@@ -16,6 +17,7 @@ ABI = _abi.load()
 EXT = _abi.load_ext()                                # the second header: ABI stays the first header's
 GLTF = _abi.load_gltf()                              # the third: tcx_gltf_animation, bound below, in none of ABI, EXT, EXPORTS
 SKIN = _abi.load_skin()                              # the fourth: tcs_skin_vertices and its tile sizes, bound below, in none of the others
+SHADE = _abi.load_shade()                            # the fifth: tcr_mesh_vertices, tcr_mesh_raster and their constants, likewise
 
 for _name, _value in {**ABI.constants, **EXT.constants}.items():          # TC_X -> X, TC_DTYPE_X -> DT_X
     globals()["DT_" + _name[9:] if _name.startswith("TC_DTYPE_") else _name[3:]] = _value
@@ -34,6 +36,7 @@ NavTrainArgs = ABI.structs["tcdiff_nav_train_args"]
 AdanScalars = ABI.structs["tcdiff_adan_scalars"]
 NavAdamWScalars = ABI.structs["tcdiff_nav_adamw_scalars"]
 DrawStyle = ABI.structs["tcdiff_draw_style"]
+ShadeStyle = SHADE.structs["tcr_shade_style"]
 
 EXPORTS = sorted({**ABI.functions, **EXT.functions})
 
@@ -67,7 +70,7 @@ def load():
         raise TcdiffError(f"{LIB_PATH} not found: build it with `python -m tcdiff_amd.build` "
                           "(the MI355X path has no CPU fallback)")
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes, _) in {**ABI.functions, **EXT.functions, **GLTF.functions, **SKIN.functions}.items():
+    for name, (restype, argtypes, _) in {**ABI.functions, **EXT.functions, **GLTF.functions, **SKIN.functions, **SHADE.functions}.items():
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = argtypes, restype
     _lib = lib

@@ -10,7 +10,8 @@ thread per pose builds the pose feature and the joints' transforms in float64, t
 shapes (a [poses x 208] x [208 x 3V] product on v_mfma_f32_32x32x2_f32) and blends the transforms per vertex, float32, one store.
 No synchronisation, no host copy, no CPU fallback.  Parity with smplx and with the official model files is unpinned: neither is a
 dependency; the definitions restate Loper et al. 2015 as smplx evaluates it and the tests hold the kernels to that restatement on
-seeded synthetic models.  Not built: shipping a model, one body shape per dancer, per-frame normals.
+seeded synthetic models.  Per-frame normals and shaded frames of the vertices: tcdiff_amd/shade.py.  Not built: shipping a model,
+one body shape per dancer.
 """
 from __future__ import annotations
 
@@ -148,11 +149,28 @@ class BodyModel:
         self.V, self.K = int(v_shaped.shape[0]), int(weight_values.shape[1])
         self._parents_c = (C.c_int * 24)(*parents)
         self._images = {}
+        self._adjacency = None
         for a in (v_shaped, J, offsets, blend, weights, weight_values, weight_joints, faces, betas):
             a.setflags(write=False)
 
+    def adjacency(self):
+        """The vertex-to-face adjacency in CSR form, ``(start int32 (V + 1,), faces int32 (3F,))``: vertex v is named by the faces
+        ``faces[start[v]:start[v + 1]]``, in ascending face index (a face that names v twice is listed twice; a vertex that no face
+        names has an empty range).  Built once with numpy and cached; what ``tcr_mesh_vertices`` sums a vertex normal over."""
+        if self._adjacency is None:
+            flat = self.faces.reshape(-1)
+            order = np.argsort(flat, kind="stable")                       # stable: ascending face index under each vertex
+            start = np.zeros(self.V + 1, np.int32)
+            start[1:] = np.cumsum(np.bincount(flat, minlength=self.V))
+            listed = (order // 3).astype(np.int32)
+            start.setflags(write=False)
+            listed.setflags(write=False)
+            self._adjacency = (start, listed)
+        return self._adjacency
+
     def images(self, device) -> dict:
-        """the float32 device images, each float64 array rounded once: v_shaped, blend, J, offsets, weights (V, K), joints (V, K) int32"""
+        """the float32 device images, each float64 array rounded once: v_shaped, blend, J, offsets, weights (V, K), joints (V, K) int32;
+        and the mesh as the shading kernels read it: faces (F, 3), adj_start (V + 1,), adj_faces (3F,), int32"""
         device = torch.device(device)
         if device.type != "cuda":
             raise L.TcdiffError("BodyModel: the device images live on MI355X only (no CPU fallback)")
@@ -163,7 +181,9 @@ class BodyModel:
                 return torch.from_numpy(np.array(a, dtype, order="C")).to(device)
             self._images[device] = {"v_shaped": up(self.v_shaped, np.float32), "blend": up(self.blend, np.float32),
                                     "J": up(self.J, np.float32), "offsets": up(self.offsets, np.float32),
-                                    "weights": up(self.weight_values, np.float32), "joints": up(self.weight_joints, np.int32)}
+                                    "weights": up(self.weight_values, np.float32), "joints": up(self.weight_joints, np.int32),
+                                    "faces": up(self.faces, np.int32), "adj_start": up(self.adjacency()[0], np.int32),
+                                    "adj_faces": up(self.adjacency()[1], np.int32)}
         return self._images[device]
 
 

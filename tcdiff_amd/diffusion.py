@@ -690,6 +690,8 @@ class GaussianDiffusion(nn.Module):
         return self.loss(x, cond, t_override, trj_dist=trj_dist)
 
     # ---- render_sample: sampling and the fk_out pose export ----------------------------------------------------------
+    body = None          # a BodyModel (tcdiff_amd/body.py load_body_model): render_sample's draw_out then shows the skinned bodies
+
     @torch.no_grad()
     def render_sample(self, shape, cond, normalizer=None, epoch=None, render_out=None, fk_out=None, name=None,
                       sound=True, mode="normal", noise=None, constraint=None, sound_folder="ood_sliced",
@@ -708,7 +710,10 @@ class GaussianDiffusion(nn.Module):
         rasteriser instead of matplotlib) and written as animated PNGs, clip by clip: ``e{epoch}_b{num}_{clip}.png`` per clip,
         or ``{epoch}_{song}.png`` of the song's first ``render_len`` frames in "long" mode -- the reference's names with the new
         extension.  No audio is muxed.  ``render_out``, ``sound``, ``sound_folder`` and ``render`` are unused: without
-        ``draw_out`` nothing is drawn.
+        ``draw_out`` nothing is drawn.  With ``self.body`` set to what ``load_body_model`` returns (an attribute, None by default: this
+        method's parameter list is pinned by the tests, so the body is no keyword here), each clip's frames are the dancers'
+        skinned, shaded bodies over that picture (tcdiff_amd/shade.py), skinned and drawn one clip at a time under the same file
+        names; ``write_draw_out(..., body=, q=, pos=)`` is the keyword form.  Without ``draw_out`` the body changes nothing.
 
         With a ``normalizer`` and a ``glb_out`` directory (keyword only), the exported poses are also written as animated glTF
         files (tcdiff_amd/gltf.py: the open counterpart of the reference's Blender_Visulization/ FBX conversion), one per clip with
@@ -727,7 +732,11 @@ class GaussianDiffusion(nn.Module):
                 write_glb_out(glb_out, mode, epoch, name, q, pos, required_dancer_num, parents=parents, offsets=offsets)
             if draw_out is not None:
                 from .draw import write_draw_out
-                write_draw_out(draw_out, mode, epoch, name, poses, contacts, render_len=render_len, parents=parents)
+                if self.body is None:
+                    write_draw_out(draw_out, mode, epoch, name, poses, contacts, render_len=render_len, parents=parents)
+                else:
+                    write_draw_out(draw_out, mode, epoch, name, poses, contacts, render_len=render_len, parents=parents,
+                                   body=self.body, q=q, pos=pos)
         return samples
 
     def _render_samples(self, shape, cond, mode, noise, constraint, start_point, x_0):

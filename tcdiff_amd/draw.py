@@ -8,7 +8,8 @@ is defined in include/tcdiff_hip.h), and an animated-PNG writer that needs the s
     write_apng("clip0.png", frames[0].cpu())                                     # host work: zlib
 
 The frames are not matplotlib's pixels: the reference draws through matplotlib's default perspective box with its own line caps
-and anti-aliasing; here the projection is orthographic at the same two view angles.  The audio is not muxed.
+and anti-aliasing; here the projection is orthographic at the same two view angles.  The audio is not muxed.  The dancers'
+skinned bodies instead of the sticks: tcdiff_amd/shade.py (``write_draw_out(..., body=...)``).
 """
 from __future__ import annotations
 
@@ -253,16 +254,31 @@ def draw_out_names(mode: str, epoch, name) -> list:
     return [f"e{epoch}_b{num}_{os.path.splitext(os.path.basename(filename))[0]}.png" for num, filename in enumerate(name)]
 
 
-def write_draw_out(draw_out, mode: str, epoch, name, poses, contacts, *, render_len=512, fps=30, **kw) -> list:
+def write_draw_out(draw_out, mode: str, epoch, name, poses, contacts, *, render_len=512, fps=30, body=None, q=None, pos=None,
+                   **kw) -> list:
     """Draws ``export_poses``' joints clip by clip -- device memory stays at one clip's frames -- and writes one animated PNG per
     clip (the first min(b, len(name)) clips, as the reference's zip), or one per song of its first ``render_len`` frames in "long"
-    mode (model/diffusion.py:921).  Returns the paths written."""
+    mode (model/diffusion.py:921).  Returns the paths written.
+
+    With a ``body`` (what ``load_body_model`` returns; keyword only) and ``export_poses``' ``q`` and ``pos``, each clip's frames
+    are its skinned bodies over the stick picture (tcdiff_amd/shade.py), skinned and drawn one clip at a time.  The file names and
+    the writer are the same."""
     names = draw_out_names(mode, epoch, name)
+    if body is not None and (q is None or pos is None):
+        raise L.TcdiffError("write_draw_out: a body needs export_poses' q and pos beside the joints")
     Path(draw_out).mkdir(parents=True, exist_ok=True)
+    dn = poses.shape[1]
     if _is_long(mode):
         poses, contacts = poses[:1, :, :render_len], None
+        if body is not None:
+            q, pos = q[:1, :render_len * dn], pos[:1, :render_len * dn]
     written = []
     for num, outname in zip(range(poses.shape[0]), names):
-        frames = draw_dance(poses[num:num + 1], None if contacts is None else contacts[num:num + 1], **kw)
+        clip = poses[num:num + 1], None if contacts is None else contacts[num:num + 1]
+        if body is None:
+            frames = draw_dance(*clip, **kw)
+        else:
+            from .shade import draw_body_poses
+            frames = draw_body_poses(body, q[num:num + 1], pos[num:num + 1], *clip, dn, **kw)
         written.append(write_apng(os.path.join(draw_out, outname), frames[0].cpu(), fps=fps))
     return written

@@ -719,3 +719,21 @@ def draw_raster(pts, trail, order, planted, b, dn, T, W, H, parents, static_segs
     L.check(L.load().tcdiff_draw_raster(_p(pts), _p(trail), _p(order), _p(planted), b, dn, T, W, H, par, _p(static_segs), n_static,
                                         _p(colors), n_colors, None if style is None else C.byref(style), out, stream()),
             "tcdiff_draw_raster")
+
+
+# ---- shaded meshes (include/tcdiff_shade.h) ----------------------------------------------------------------------------------
+def mesh_vertices(vertices, faces, adj_start, adj_faces, P, V, F, view, screen, normals):
+    """vertices (P, V, 3) fp32 contiguous; faces (F, 3) int32; the CSR adjacency; view: 12 floats; screen / normals (P, V, 3) or None"""
+    v = None if view is None else (C.c_float * 12)(*[float(x) for x in view])
+    L.check(L.load().tcr_mesh_vertices(_p(vertices), _p(faces), _p(adj_start), _p(adj_faces), P, V, F, v, _p(screen), _p(normals),
+                                       stream()), "tcr_mesh_vertices")
+
+
+def mesh_raster(screen, normals, faces, b, T, dn, V, F, W, H, colors, n_colors, style, under, scratch, frames):
+    """style: an _lib.ShadeStyle; scratch: an int32 tensor; frames: a uint8 tensor or a device address (frames placed inside a
+    larger buffer)"""
+    out = frames if frames is None or isinstance(frames, int) else frames.data_ptr()
+    L.check(L.load().tcr_mesh_raster(_p(screen), _p(normals), _p(faces), b, T, dn, V, F, W, H, _p(colors), n_colors,
+                                     None if style is None else C.byref(style), _p(under), _p(scratch),
+                                     0 if scratch is None else scratch.numel() * scratch.element_size(), out, stream()),
+            "tcr_mesh_raster")
