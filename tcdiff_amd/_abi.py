@@ -1,7 +1,7 @@
 """The C ABI of libtcdiff_gfx950.so, read from include/tcdiff_hip.h: its integer macros, structs and prototypes as ctypes.
 include/tcdiff_hip_ext.h, the launchers added since the first header was pinned, is read the same way (load_ext), and so is
-include/tcdiff_gltf.h, whose function carries the prefix tcx_ (load_gltf), include/tcdiff_skin.h, prefix tcs_ (load_skin), and include/tcdiff_shade.h,
-prefix tcr_ (load_shade).
+include/tcdiff_gltf.h, whose function carries the prefix tcx_ (load_gltf), include/tcdiff_skin.h, prefix tcs_ (load_skin), include/tcdiff_shade.h,
+prefix tcr_ (load_shade), and include/tcdiff_mjpeg.h, prefix tcj_ (load_mjpeg).
 
 The headers are the one place where the ABI is written down; _lib.py binds the library from what parse() returns.  The parser
 knows the C that the header uses and nothing more, and it never guesses: a declaration it does not recognise raises
@@ -17,6 +17,7 @@ HEADER_EXT = os.path.join(os.path.dirname(HEADER), "tcdiff_hip_ext.h")
 HEADER_GLTF = os.path.join(os.path.dirname(HEADER), "tcdiff_gltf.h")
 HEADER_SKIN = os.path.join(os.path.dirname(HEADER), "tcdiff_skin.h")
 HEADER_SHADE = os.path.join(os.path.dirname(HEADER), "tcdiff_shade.h")
+HEADER_MJPEG = os.path.join(os.path.dirname(HEADER), "tcdiff_mjpeg.h")
 
 
 class TcdiffError(RuntimeError):
@@ -165,3 +166,10 @@ def load_shade() -> Abi:
     and chunk sizes as constants; tcr_* because tcdiff_*, tcx_* and tcs_* are frozen"""
     with open(HEADER_SHADE) as f:
         return parse(f.read(), "include/tcdiff_shade.h", prefix="tcr_")
+
+
+def load_mjpeg() -> Abi:
+    """the sixth header: the Motion-JPEG encoder's three launchers, tcj_mjpeg_workspace, tcj_mjpeg_plan and tcj_mjpeg_write, and its
+    constants; tcj_* because tcdiff_*, tcx_*, tcs_* and tcr_* are frozen"""
+    with open(HEADER_MJPEG) as f:
+        return parse(f.read(), "include/tcdiff_mjpeg.h", prefix="tcj_")

@@ -691,6 +691,8 @@ class GaussianDiffusion(nn.Module):
 
     # ---- render_sample: sampling and the fk_out pose export ----------------------------------------------------------
     body = None          # a BodyModel (tcdiff_amd/body.py load_body_model): render_sample's draw_out then shows the skinned bodies
+    draw_format = "png"          # "avi": render_sample's draw_out writes Motion-JPEG AVI files (tcdiff_amd/video.py), with the clips' music if `sound`
+    draw_audio_folder = None     # where the clips' .wav files are looked up by basename; None: beside the names
 
     @torch.no_grad()
     def render_sample(self, shape, cond, normalizer=None, epoch=None, render_out=None, fk_out=None, name=None,
@@ -709,8 +711,12 @@ class GaussianDiffusion(nn.Module):
         (tcdiff_amd/draw.py: the bones, floor trail and foot markers of ``skeleton_render``, vis.py:223-327, by a HIP
         rasteriser instead of matplotlib) and written as animated PNGs, clip by clip: ``e{epoch}_b{num}_{clip}.png`` per clip,
         or ``{epoch}_{song}.png`` of the song's first ``render_len`` frames in "long" mode -- the reference's names with the new
-        extension.  No audio is muxed.  ``render_out``, ``sound``, ``sound_folder`` and ``render`` are unused: without
-        ``draw_out`` nothing is drawn.  With ``self.body`` set to what ``load_body_model`` returns (an attribute, None by default: this
+        extension.  An animated PNG has no sound: ``render_out``, ``sound``, ``sound_folder`` and ``render`` are unused with it, and
+        without ``draw_out`` nothing is drawn.  With ``self.draw_format = "avi"`` (an attribute, "png" by default, for the reason
+        given for ``body`` below) the files are Motion-JPEG AVI instead (tcdiff_amd/video.py), encoded on the device, and if
+        ``sound`` is true each carries its clip's music as the reference finds it (``clip_audio``: the .wav beside each name, or in
+        ``self.draw_audio_folder``; "long" mode stitches the windows' files); a .wav that does not exist raises before the
+        sampler runs.  With ``self.body`` set to what ``load_body_model`` returns (an attribute, None by default: this
         method's parameter list is pinned by the tests, so the body is no keyword here), each clip's frames are the dancers'
         skinned, shaded bodies over that picture (tcdiff_amd/shade.py), skinned and drawn one clip at a time under the same file
         names; ``write_draw_out(..., body=, q=, pos=)`` is the keyword form.  Without ``draw_out`` the body changes nothing.
@@ -719,6 +725,12 @@ class GaussianDiffusion(nn.Module):
         files (tcdiff_amd/gltf.py: the open counterpart of the reference's Blender_Visulization/ FBX conversion), one per clip with
         all its dancers, under ``fk_out``'s names with the extension .glb.  The export runs once whichever of the three asks.
         The samples are returned either way (the reference returns None)."""
+        if self.draw_format not in ("png", "avi"):
+            raise L.TcdiffError(f'render_sample: draw_format must be "png" or "avi", got {self.draw_format!r}')
+        with_sound = normalizer is not None and draw_out is not None and self.draw_format == "avi" and bool(sound)
+        if with_sound:
+            from .video import clip_audio, clip_audio_paths
+            clip_audio_paths(name, mode, self.draw_audio_folder)          # a missing .wav is an error before any sampling
         samples = self._render_samples(shape, cond, mode, noise, constraint, start_point, x_0)
         if normalizer is not None and (fk_out is not None or draw_out is not None or glb_out is not None):
             from .export import export_poses, write_fk_out
@@ -732,11 +744,10 @@ class GaussianDiffusion(nn.Module):
                 write_glb_out(glb_out, mode, epoch, name, q, pos, required_dancer_num, parents=parents, offsets=offsets)
             if draw_out is not None:
                 from .draw import write_draw_out
-                if self.body is None:
-                    write_draw_out(draw_out, mode, epoch, name, poses, contacts, render_len=render_len, parents=parents)
-                else:
-                    write_draw_out(draw_out, mode, epoch, name, poses, contacts, render_len=render_len, parents=parents,
-                                   body=self.body, q=q, pos=pos)
+                kw = {} if self.body is None else dict(body=self.body, q=q, pos=pos)
+                if self.draw_format == "avi":
+                    kw.update(format="avi", audio=clip_audio(name, mode, self.draw_audio_folder, x.device) if with_sound else None)
+                write_draw_out(draw_out, mode, epoch, name, poses, contacts, render_len=render_len, parents=parents, **kw)
         return samples
 
     def _render_samples(self, shape, cond, mode, noise, constraint, start_point, x_0):

@@ -8,7 +8,8 @@ is defined in include/tcdiff_hip.h), and an animated-PNG writer that needs the s
     write_apng("clip0.png", frames[0].cpu())                                     # host work: zlib
 
 The frames are not matplotlib's pixels: the reference draws through matplotlib's default perspective box with its own line caps
-and anti-aliasing; here the projection is orthographic at the same two view angles.  The audio is not muxed.  The dancers'
+and anti-aliasing; here the projection is orthographic at the same two view angles.  An animated PNG has no sound; the clip with
+its music is ``write_draw_out(..., format="avi")`` (tcdiff_amd/video.py: Motion-JPEG AVI, encoded on the device).  The dancers'
 skinned bodies instead of the sticks: tcdiff_amd/shade.py (``write_draw_out(..., body=...)``).
 """
 from __future__ import annotations
@@ -211,7 +212,7 @@ def write_apng(path, frames, fps=30, level=6) -> str:
     """frames: host uint8 (T, H, W, 3) RGB, a numpy array or a CPU tensor -> an animated PNG at ``path``: IHDR, acTL, then per
     frame fcTL + IDAT (frame 0) or fdAT (later frames), IEND.  Full frames, filter 0 on every row, a delay of 1 / fps seconds,
     looping forever; any PNG viewer shows frame 0 and browsers play it.  ``zlib`` and ``struct`` only.  The compression is host
-    work (profiles/draw.txt).  No audio is muxed."""
+    work (profiles/draw.txt).  No audio: tcdiff_amd/video.py writes the clip with its music."""
     if isinstance(frames, torch.Tensor):
         if frames.is_cuda:
             raise L.TcdiffError("write_apng: frames must be on the host (frames.cpu()); the encode is host work")
@@ -255,15 +256,27 @@ def draw_out_names(mode: str, epoch, name) -> list:
 
 
 def write_draw_out(draw_out, mode: str, epoch, name, poses, contacts, *, render_len=512, fps=30, body=None, q=None, pos=None,
-                   **kw) -> list:
+                   format="png", quality=90, subsampling="420", audio=None, **kw) -> list:
     """Draws ``export_poses``' joints clip by clip -- device memory stays at one clip's frames -- and writes one animated PNG per
     clip (the first min(b, len(name)) clips, as the reference's zip), or one per song of its first ``render_len`` frames in "long"
     mode (model/diffusion.py:921).  Returns the paths written.
 
     With a ``body`` (what ``load_body_model`` returns; keyword only) and ``export_poses``' ``q`` and ``pos``, each clip's frames
     are its skinned bodies over the stick picture (tcdiff_amd/shade.py), skinned and drawn one clip at a time.  The file names and
-    the writer are the same."""
+    the writer are the same.
+
+    ``format="avi"`` (keyword only) writes Motion-JPEG AVI files under the same names with the extension .avi instead
+    (tcdiff_amd/video.py): each clip's frames are encoded on the device at ``quality`` and ``subsampling``, and only the compressed
+    bytes cross to the host.  ``audio``: a list of (samples, sample_rate) per written file, or None for files without sound."""
+    if format not in ("png", "avi"):
+        raise L.TcdiffError(f'write_draw_out: format must be "png" or "avi", got {format!r}')
     names = draw_out_names(mode, epoch, name)
+    if format == "avi":
+        names = [os.path.splitext(n)[0] + ".avi" for n in names]
+        if audio is not None and len(audio) < min(poses.shape[0], len(names)):
+            raise L.TcdiffError(f"write_draw_out: {len(audio)} audio tracks for {min(poses.shape[0], len(names))} files")
+    elif audio is not None:
+        raise L.TcdiffError("write_draw_out: an animated PNG carries no audio (format=\"avi\" does)")
     if body is not None and (q is None or pos is None):
         raise L.TcdiffError("write_draw_out: a body needs export_poses' q and pos beside the joints")
     Path(draw_out).mkdir(parents=True, exist_ok=True)
@@ -280,5 +293,11 @@ def write_draw_out(draw_out, mode: str, epoch, name, poses, contacts, *, render_
         else:
             from .shade import draw_body_poses
             frames = draw_body_poses(body, q[num:num + 1], pos[num:num + 1], *clip, dn, **kw)
+        if format == "avi":
+            from .video import encode_jpeg, write_avi
+            samples, rate = (None, None) if audio is None else audio[num]
+            written.append(write_avi(os.path.join(draw_out, outname), encode_jpeg(frames[0], quality, subsampling), fps=fps,
+                                     audio=samples, sample_rate=rate))
+            continue
         written.append(write_apng(os.path.join(draw_out, outname), frames[0].cpu(), fps=fps))
     return written

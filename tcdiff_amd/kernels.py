@@ -737,3 +737,27 @@ def mesh_raster(screen, normals, faces, b, T, dn, V, F, W, H, colors, n_colors, 
                                      None if style is None else C.byref(style), _p(under), _p(scratch),
                                      0 if scratch is None else scratch.numel() * scratch.element_size(), out, stream()),
             "tcr_mesh_raster")
+
+
+# ---- Motion-JPEG frames (include/tcdiff_mjpeg.h) -------------------------------------------------------------------------------
+def mjpeg_workspace(N, H, W, subsampling) -> int:
+    """the bytes of workspace mjpeg_plan and mjpeg_write need"""
+    n = C.c_long(0)
+    L.check(L.load().tcj_mjpeg_workspace(N, H, W, subsampling, C.byref(n)), "tcj_mjpeg_workspace")
+    return n.value
+
+
+def mjpeg_plan(frames, quality, subsampling, workspace, offsets):
+    """frames (N, H, W, 3) uint8, read through its strides; workspace: a uint8 tensor; offsets (N + 1,) int64"""
+    N, H, W, _ = frames.shape
+    strides = (C.c_long * 3)(*frames.stride()[:3])
+    L.check(L.load().tcj_mjpeg_plan(_p(frames), strides, N, H, W, quality, subsampling, _p(workspace),
+                                    0 if workspace is None else workspace.numel() * workspace.element_size(), _p(offsets), stream()),
+            "tcj_mjpeg_plan")
+
+
+def mjpeg_write(N, H, W, quality, subsampling, workspace, data):
+    """data: a uint8 tensor of at least offsets[N] bytes (a view inside a larger buffer is written in place)"""
+    L.check(L.load().tcj_mjpeg_write(N, H, W, quality, subsampling, _p(workspace),
+                                     0 if workspace is None else workspace.numel() * workspace.element_size(), _p(data),
+                                     0 if data is None else data.numel(), stream()), "tcj_mjpeg_write")
