@@ -18,6 +18,7 @@ from .gltf import animation_block, build_glb, write_glb, write_glb_out, convert_
 from .body import BodyModel, load_body_model, skin  # noqa: F401
 from .shade import vertex_normals, draw_bodies, draw_body_samples  # noqa: F401
 from .video import JpegFrames, encode_jpeg, jpeg_tables, pcm16, write_avi, clip_audio  # noqa: F401
+from .footlock import FootLock, foot_lock  # noqa: F401
 from .audio import WavData, read_wav, decode, resample, slice_audio, load_audio  # noqa: F401
 
 __all__ = ["DanceDecoder", "GaussianDiffusion", "EMA", "Adan", "SMPLSkeleton", "ax_from_6v", "TrajDecoder", "TrajTrainer", "TrajAdamW",

@@ -1,7 +1,7 @@
 """The C ABI of libtcdiff_gfx950.so, read from include/tcdiff_hip.h: its integer macros, structs and prototypes as ctypes.
 include/tcdiff_hip_ext.h, the launchers added since the first header was pinned, is read the same way (load_ext), and so is
 include/tcdiff_gltf.h, whose function carries the prefix tcx_ (load_gltf), include/tcdiff_skin.h, prefix tcs_ (load_skin), include/tcdiff_shade.h,
-prefix tcr_ (load_shade), and include/tcdiff_mjpeg.h, prefix tcj_ (load_mjpeg).
+prefix tcr_ (load_shade), include/tcdiff_mjpeg.h, prefix tcj_ (load_mjpeg), and include/tcdiff_footlock.h, prefix tck_ (load_footlock).
 
 The headers are the one place where the ABI is written down; _lib.py binds the library from what parse() returns.  The parser
 knows the C that the header uses and nothing more, and it never guesses: a declaration it does not recognise raises
@@ -18,6 +18,7 @@ HEADER_GLTF = os.path.join(os.path.dirname(HEADER), "tcdiff_gltf.h")
 HEADER_SKIN = os.path.join(os.path.dirname(HEADER), "tcdiff_skin.h")
 HEADER_SHADE = os.path.join(os.path.dirname(HEADER), "tcdiff_shade.h")
 HEADER_MJPEG = os.path.join(os.path.dirname(HEADER), "tcdiff_mjpeg.h")
+HEADER_FOOTLOCK = os.path.join(os.path.dirname(HEADER), "tcdiff_footlock.h")
 
 
 class TcdiffError(RuntimeError):
@@ -173,3 +174,10 @@ def load_mjpeg() -> Abi:
     constants; tcj_* because tcdiff_*, tcx_*, tcs_* and tcr_* are frozen"""
     with open(HEADER_MJPEG) as f:
         return parse(f.read(), "include/tcdiff_mjpeg.h", prefix="tcj_")
+
+
+def load_footlock() -> Abi:
+    """the seventh header: the foot lock's two functions, tck_foot_lock_workspace and tck_foot_lock, and its constants; tck_* because
+    tcdiff_*, tcx_*, tcs_*, tcr_* and tcj_* are frozen"""
+    with open(HEADER_FOOTLOCK) as f:
+        return parse(f.read(), "include/tcdiff_footlock.h", prefix="tck_")

@@ -693,6 +693,7 @@ class GaussianDiffusion(nn.Module):
     body = None          # a BodyModel (tcdiff_amd/body.py load_body_model): render_sample's draw_out then shows the skinned bodies
     draw_format = "png"          # "avi": render_sample's draw_out writes Motion-JPEG AVI files (tcdiff_amd/video.py), with the clips' music if `sound`
     draw_audio_folder = None     # where the clips' .wav files are looked up by basename; None: beside the names
+    foot_lock = False            # True: render_sample pins the planted feet (tcdiff_amd/footlock.py) before anything is written
 
     @torch.no_grad()
     def render_sample(self, shape, cond, normalizer=None, epoch=None, render_out=None, fk_out=None, name=None,
@@ -724,6 +725,9 @@ class GaussianDiffusion(nn.Module):
         With a ``normalizer`` and a ``glb_out`` directory (keyword only), the exported poses are also written as animated glTF
         files (tcdiff_amd/gltf.py: the open counterpart of the reference's Blender_Visulization/ FBX conversion), one per clip with
         all its dancers, under ``fk_out``'s names with the extension .glb.  The export runs once whichever of the three asks.
+        With ``self.foot_lock = True`` (an attribute, False by default, for the same reason as ``body``) the exported poses pass
+        through ``foot_lock`` once -- the planted feet pinned, hip and knee re-solved (tcdiff_amd/footlock.py) -- and every writer
+        gets the locked ``q`` and joints in place of the raw ones; with it False nothing changes.
         The samples are returned either way (the reference returns None)."""
         if self.draw_format not in ("png", "avi"):
             raise L.TcdiffError(f'render_sample: draw_format must be "png" or "avi", got {self.draw_format!r}')
@@ -737,6 +741,10 @@ class GaussianDiffusion(nn.Module):
             x = samples if samples.is_cuda else samples.to(self._device())
             parents, offsets = self._skeleton(x.device)
             q, pos, poses, contacts = export_poses(x, normalizer, mode, required_dancer_num, parents=parents, offsets=offsets)
+            if self.foot_lock:
+                from .footlock import foot_lock
+                locked = foot_lock(q, pos, contacts, dn=int(required_dancer_num), parents=parents, offsets=offsets)
+                q, poses = locked.q, locked.joints
             if fk_out is not None:
                 write_fk_out(fk_out, mode, epoch, name, q, pos, poses)
             if glb_out is not None:

@@ -761,3 +761,22 @@ def mjpeg_write(N, H, W, quality, subsampling, workspace, data):
     L.check(L.load().tcj_mjpeg_write(N, H, W, quality, subsampling, _p(workspace),
                                      0 if workspace is None else workspace.numel() * workspace.element_size(), _p(data),
                                      0 if data is None else data.numel(), stream()), "tcj_mjpeg_write")
+
+
+# ---- the foot lock (include/tcdiff_footlock.h) ---------------------------------------------------------------------------------
+def foot_lock_workspace(b, dn, T) -> int:
+    """the bytes of workspace foot_lock needs"""
+    n = C.c_long(0)
+    L.check(L.load().tck_foot_lock_workspace(b, dn, T, C.byref(n)), "tck_foot_lock_workspace")
+    return n.value
+
+
+def foot_lock(q, pos, contacts, b, dn, T, contact_threshold, still, blend, reach, parents, offsets, workspace, q_out, joints, planted,
+              clamped, max_shift):
+    """q (b, T dn, 24, 3) / pos (b, T dn, 3) fp32 contiguous; contacts (b, dn, T, 4) fp32 view read by its strides, or None; workspace:
+    a uint8 tensor; q_out like q; joints (b, dn, T, 24, 3) or None; planted, clamped (b, dn, 2) int32; max_shift (b, dn, 2) float64.
+    Three launches."""
+    L.check(L.load().tck_foot_lock(_p(q), _p(pos), _p(contacts), _strides(contacts, 4), b, dn, T, contact_threshold, still, blend, reach,
+                                   *_skeleton(parents, offsets), _p(workspace),
+                                   0 if workspace is None else workspace.numel() * workspace.element_size(), _p(q_out), _p(joints),
+                                   _p(planted), _p(clamped), _p(max_shift), stream()), "tck_foot_lock")
