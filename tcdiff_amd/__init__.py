@@ -19,6 +19,7 @@ from .body import BodyModel, load_body_model, skin  # noqa: F401
 from .shade import vertex_normals, draw_bodies, draw_body_samples  # noqa: F401
 from .video import JpegFrames, encode_jpeg, jpeg_tables, pcm16, write_avi, clip_audio  # noqa: F401
 from .footlock import FootLock, foot_lock  # noqa: F401
+from .group_metrics import group_metrics, pairs, capsule_radii, radii_from_body, evaluate_group  # noqa: F401
 from .audio import WavData, read_wav, decode, resample, slice_audio, load_audio  # noqa: F401
 
 __all__ = ["DanceDecoder", "GaussianDiffusion", "EMA", "Adan", "SMPLSkeleton", "ax_from_6v", "TrajDecoder", "TrajTrainer", "TrajAdamW",
@@ -28,4 +29,5 @@ __all__ = ["DanceDecoder", "GaussianDiffusion", "EMA", "Adan", "SMPLSkeleton", "
            "music_features", "assemble_cond",
            "beat_track", "music_cond", "chroma_cqt", "estimate_tuning", "wav_cond", "WavData", "read_wav", "decode", "resample",
            "slice_audio", "load_audio", "animation_block", "build_glb", "write_glb", "write_glb_out", "convert_fk_out",
-           "BodyModel", "load_body_model", "skin", "vertex_normals", "draw_bodies", "draw_body_samples"]
+           "BodyModel", "load_body_model", "skin", "vertex_normals", "draw_bodies", "draw_body_samples",
+           "group_metrics", "pairs", "capsule_radii", "radii_from_body", "evaluate_group"]

@@ -1,7 +1,7 @@
 """The C ABI of libtcdiff_gfx950.so, read from include/tcdiff_hip.h: its integer macros, structs and prototypes as ctypes.
 include/tcdiff_hip_ext.h, the launchers added since the first header was pinned, is read the same way (load_ext), and so is
 include/tcdiff_gltf.h, whose function carries the prefix tcx_ (load_gltf), include/tcdiff_skin.h, prefix tcs_ (load_skin), include/tcdiff_shade.h,
-prefix tcr_ (load_shade), include/tcdiff_mjpeg.h, prefix tcj_ (load_mjpeg), and include/tcdiff_footlock.h, prefix tck_ (load_footlock).
+prefix tcr_ (load_shade), include/tcdiff_mjpeg.h, prefix tcj_ (load_mjpeg), include/tcdiff_footlock.h, prefix tck_ (load_footlock), and include/tcdiff_group.h, prefix tcg_ (load_group).
 
 The headers are the one place where the ABI is written down; _lib.py binds the library from what parse() returns.  The parser
 knows the C that the header uses and nothing more, and it never guesses: a declaration it does not recognise raises
@@ -19,6 +19,7 @@ HEADER_SKIN = os.path.join(os.path.dirname(HEADER), "tcdiff_skin.h")
 HEADER_SHADE = os.path.join(os.path.dirname(HEADER), "tcdiff_shade.h")
 HEADER_MJPEG = os.path.join(os.path.dirname(HEADER), "tcdiff_mjpeg.h")
 HEADER_FOOTLOCK = os.path.join(os.path.dirname(HEADER), "tcdiff_footlock.h")
+HEADER_GROUP = os.path.join(os.path.dirname(HEADER), "tcdiff_group.h")
 
 
 class TcdiffError(RuntimeError):
@@ -181,3 +182,10 @@ def load_footlock() -> Abi:
     tcdiff_*, tcx_*, tcs_*, tcr_* and tcj_* are frozen"""
     with open(HEADER_FOOTLOCK) as f:
         return parse(f.read(), "include/tcdiff_footlock.h", prefix="tck_")
+
+
+def load_group() -> Abi:
+    """the eighth header: the group metrics' two functions, tcg_group_workspace and tcg_group_metrics, and its constants; tcg_* because
+    tcdiff_*, tcx_*, tcs_*, tcr_*, tcj_* and tck_* are frozen"""
+    with open(HEADER_GROUP) as f:
+        return parse(f.read(), "include/tcdiff_group.h", prefix="tcg_")

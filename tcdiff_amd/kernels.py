@@ -780,3 +780,23 @@ def foot_lock(q, pos, contacts, b, dn, T, contact_threshold, still, blend, reach
                                    *_skeleton(parents, offsets), _p(workspace),
                                    0 if workspace is None else workspace.numel() * workspace.element_size(), _p(q_out), _p(joints),
                                    _p(planted), _p(clamped), _p(max_shift), stream()), "tck_foot_lock")
+
+
+# ---- the group metrics (include/tcdiff_group.h) --------------------------------------------------------------------------------
+def group_workspace(b, dn, T, max_lag) -> int:
+    """the bytes of workspace group_metrics needs"""
+    n = C.c_long(0)
+    L.check(L.load().tcg_group_workspace(b, dn, T, max_lag, C.byref(n)), "tcg_group_workspace")
+    return n.value
+
+
+def group_metrics(joints, up, fps, parents, radii, window, max_lag, sigma_floor, workspace, gap, closest, contact_rate, gap_min, episodes,
+                  closest_min, crossings, crossing_rate, sync, sync_lag, sync_zero):
+    """joints (b, dn, T, 24, 3) fp32 view, read by its strides; parents: 24 ints, radii: 24 floats (host); workspace: a uint8 tensor;
+    gap (b, P, T) float64 / closest (b, P, T) int32 contiguous or None; the nine (b, P) outputs, closest_min (b, P, 3).  Three launches."""
+    b, dn, T = joints.shape[:3]
+    L.check(L.load().tcg_group_metrics(_p(joints), _strides(joints, 3), b, dn, T, up, fps, (C.c_int * 24)(*parents), (C.c_double * 24)(*radii),
+                                       window, max_lag, sigma_floor, _p(workspace),
+                                       0 if workspace is None else workspace.numel() * workspace.element_size(), _p(gap), _p(closest),
+                                       _p(contact_rate), _p(gap_min), _p(episodes), _p(closest_min), _p(crossings), _p(crossing_rate),
+                                       _p(sync), _p(sync_lag), _p(sync_zero), stream()), "tcg_group_metrics")
