@@ -1,7 +1,8 @@
 """The C ABI of libtcdiff_gfx950.so, read from include/tcdiff_hip.h: its integer macros, structs and prototypes as ctypes.
 include/tcdiff_hip_ext.h, the launchers added since the first header was pinned, is read the same way (load_ext), and so is
 include/tcdiff_gltf.h, whose function carries the prefix tcx_ (load_gltf), include/tcdiff_skin.h, prefix tcs_ (load_skin), include/tcdiff_shade.h,
-prefix tcr_ (load_shade), include/tcdiff_mjpeg.h, prefix tcj_ (load_mjpeg), include/tcdiff_footlock.h, prefix tck_ (load_footlock), and include/tcdiff_group.h, prefix tcg_ (load_group).
+prefix tcr_ (load_shade), include/tcdiff_mjpeg.h, prefix tcj_ (load_mjpeg), include/tcdiff_footlock.h, prefix tck_ (load_footlock), include/tcdiff_group.h, prefix tcg_ (load_group), and
+include/tcdiff_apart.h, prefix tcp_ (load_apart).
 
 The headers are the one place where the ABI is written down; _lib.py binds the library from what parse() returns.  The parser
 knows the C that the header uses and nothing more, and it never guesses: a declaration it does not recognise raises
@@ -20,6 +21,7 @@ HEADER_SHADE = os.path.join(os.path.dirname(HEADER), "tcdiff_shade.h")
 HEADER_MJPEG = os.path.join(os.path.dirname(HEADER), "tcdiff_mjpeg.h")
 HEADER_FOOTLOCK = os.path.join(os.path.dirname(HEADER), "tcdiff_footlock.h")
 HEADER_GROUP = os.path.join(os.path.dirname(HEADER), "tcdiff_group.h")
+HEADER_APART = os.path.join(os.path.dirname(HEADER), "tcdiff_apart.h")
 
 
 class TcdiffError(RuntimeError):
@@ -189,3 +191,10 @@ def load_group() -> Abi:
     tcdiff_*, tcx_*, tcs_*, tcr_*, tcj_* and tck_* are frozen"""
     with open(HEADER_GROUP) as f:
         return parse(f.read(), "include/tcdiff_group.h", prefix="tcg_")
+
+
+def load_apart() -> Abi:
+    """the ninth header: keeping the dancers apart, tcp_keep_apart_workspace and tcp_keep_apart, and its constants; tcp_* because
+    tcdiff_*, tcx_*, tcs_*, tcr_*, tcj_*, tck_* and tcg_* are frozen"""
+    with open(HEADER_APART) as f:
+        return parse(f.read(), "include/tcdiff_apart.h", prefix="tcp_")

@@ -694,6 +694,7 @@ class GaussianDiffusion(nn.Module):
     draw_format = "png"          # "avi": render_sample's draw_out writes Motion-JPEG AVI files (tcdiff_amd/video.py), with the clips' music if `sound`
     draw_audio_folder = None     # where the clips' .wav files are looked up by basename; None: beside the names
     foot_lock = False            # True: render_sample pins the planted feet (tcdiff_amd/footlock.py) before anything is written
+    keep_apart = False           # True: render_sample first shifts the roots so that the bodies do not touch (tcdiff_amd/apart.py)
 
     @torch.no_grad()
     def render_sample(self, shape, cond, normalizer=None, epoch=None, render_out=None, fk_out=None, name=None,
@@ -728,6 +729,9 @@ class GaussianDiffusion(nn.Module):
         With ``self.foot_lock = True`` (an attribute, False by default, for the same reason as ``body``) the exported poses pass
         through ``foot_lock`` once -- the planted feet pinned, hip and knee re-solved (tcdiff_amd/footlock.py) -- and every writer
         gets the locked ``q`` and joints in place of the raw ones; with it False nothing changes.
+        With ``self.keep_apart = True`` (likewise an attribute, False by default) ``keep_apart`` runs first, right after the export
+        (tcdiff_amd/apart.py: the roots shifted horizontally so that the dancers' bodies do not touch), and the foot lock and every
+        writer get the shifted ``pos`` and joints; with it False nothing changes.
         The samples are returned either way (the reference returns None)."""
         if self.draw_format not in ("png", "avi"):
             raise L.TcdiffError(f'render_sample: draw_format must be "png" or "avi", got {self.draw_format!r}')
@@ -741,6 +745,9 @@ class GaussianDiffusion(nn.Module):
             x = samples if samples.is_cuda else samples.to(self._device())
             parents, offsets = self._skeleton(x.device)
             q, pos, poses, contacts = export_poses(x, normalizer, mode, required_dancer_num, parents=parents, offsets=offsets)
+            if self.keep_apart:          # before the foot lock: a shifted root slides a planted foot, and the lock re-pins it
+                from .apart import keep_apart
+                pos, poses = keep_apart(pos, poses, dn=int(required_dancer_num), parents=parents)[:2]
             if self.foot_lock:
                 from .footlock import foot_lock
                 locked = foot_lock(q, pos, contacts, dn=int(required_dancer_num), parents=parents, offsets=offsets)

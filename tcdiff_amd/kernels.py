@@ -800,3 +800,24 @@ def group_metrics(joints, up, fps, parents, radii, window, max_lag, sigma_floor,
                                        0 if workspace is None else workspace.numel() * workspace.element_size(), _p(gap), _p(closest),
                                        _p(contact_rate), _p(gap_min), _p(episodes), _p(closest_min), _p(crossings), _p(crossing_rate),
                                        _p(sync), _p(sync_lag), _p(sync_zero), stream()), "tcg_group_metrics")
+
+
+# ---- keeping the dancers apart (include/tcdiff_apart.h) -------------------------------------------------------------------------
+def keep_apart_workspace(b, dn, T) -> int:
+    """the bytes of workspace keep_apart needs"""
+    n = C.c_long(0)
+    L.check(L.load().tcp_keep_apart_workspace(b, dn, T, C.byref(n)), "tcp_keep_apart_workspace")
+    return n.value
+
+
+def keep_apart(pos, joints, up, parents, radii, mobility, margin, iterations, rounds, blend, max_push, workspace, pos_out, joints_out, shift,
+               contact_before, contact_after, gap_min_before, gap_min_after, pushed, capped, max_shift, max_step):
+    """pos (b, T dn, 3) fp32 contiguous; joints (b, dn, T, 24, 3) fp32 view, read by its strides; parents: 24 ints, radii: 24 floats,
+    mobility: dn floats (host); workspace: a uint8 tensor; pos_out / joints_out contiguous; shift (b, dn, T, 2) float64 or None; the
+    six (b, P) and two (b, dn) outputs.  2 rounds + 3 launches."""
+    b, dn, T = joints.shape[:3]
+    L.check(L.load().tcp_keep_apart(_p(pos), _p(joints), _strides(joints, 3), b, dn, T, up, (C.c_int * 24)(*parents), (C.c_double * 24)(*radii),
+                                    (C.c_double * dn)(*mobility), margin, iterations, rounds, blend, max_push, _p(workspace),
+                                    0 if workspace is None else workspace.numel() * workspace.element_size(), _p(pos_out), _p(joints_out),
+                                    _p(shift), _p(contact_before), _p(contact_after), _p(gap_min_before), _p(gap_min_after), _p(pushed),
+                                    _p(capped), _p(max_shift), _p(max_step), stream()), "tcp_keep_apart")
