@@ -21,6 +21,7 @@ from .video import JpegFrames, encode_jpeg, jpeg_tables, pcm16, write_avi, clip_
 from .footlock import FootLock, foot_lock  # noqa: F401
 from .group_metrics import group_metrics, pairs, capsule_radii, radii_from_body, evaluate_group  # noqa: F401
 from .apart import Apart, keep_apart  # noqa: F401
+from .ground import Ground, ground, ground_metrics  # noqa: F401
 from .audio import WavData, read_wav, decode, resample, slice_audio, load_audio  # noqa: F401
 
 __all__ = ["DanceDecoder", "GaussianDiffusion", "EMA", "Adan", "SMPLSkeleton", "ax_from_6v", "TrajDecoder", "TrajTrainer", "TrajAdamW",
@@ -31,4 +32,5 @@ __all__ = ["DanceDecoder", "GaussianDiffusion", "EMA", "Adan", "SMPLSkeleton", "
            "beat_track", "music_cond", "chroma_cqt", "estimate_tuning", "wav_cond", "WavData", "read_wav", "decode", "resample",
            "slice_audio", "load_audio", "animation_block", "build_glb", "write_glb", "write_glb_out", "convert_fk_out",
            "BodyModel", "load_body_model", "skin", "vertex_normals", "draw_bodies", "draw_body_samples",
-           "group_metrics", "pairs", "capsule_radii", "radii_from_body", "evaluate_group", "Apart", "keep_apart"]
+           "group_metrics", "pairs", "capsule_radii", "radii_from_body", "evaluate_group", "Apart", "keep_apart",
+           "Ground", "ground", "ground_metrics"]

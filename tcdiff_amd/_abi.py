@@ -1,8 +1,8 @@
 """The C ABI of libtcdiff_gfx950.so, read from include/tcdiff_hip.h: its integer macros, structs and prototypes as ctypes.
 include/tcdiff_hip_ext.h, the launchers added since the first header was pinned, is read the same way (load_ext), and so is
 include/tcdiff_gltf.h, whose function carries the prefix tcx_ (load_gltf), include/tcdiff_skin.h, prefix tcs_ (load_skin), include/tcdiff_shade.h,
-prefix tcr_ (load_shade), include/tcdiff_mjpeg.h, prefix tcj_ (load_mjpeg), include/tcdiff_footlock.h, prefix tck_ (load_footlock), include/tcdiff_group.h, prefix tcg_ (load_group), and
-include/tcdiff_apart.h, prefix tcp_ (load_apart).
+prefix tcr_ (load_shade), include/tcdiff_mjpeg.h, prefix tcj_ (load_mjpeg), include/tcdiff_footlock.h, prefix tck_ (load_footlock), include/tcdiff_group.h, prefix tcg_ (load_group),
+include/tcdiff_apart.h, prefix tcp_ (load_apart), and include/tcdiff_ground.h, prefix tcf_ (load_ground).
 
 The headers are the one place where the ABI is written down; _lib.py binds the library from what parse() returns.  The parser
 knows the C that the header uses and nothing more, and it never guesses: a declaration it does not recognise raises
@@ -22,6 +22,7 @@ HEADER_MJPEG = os.path.join(os.path.dirname(HEADER), "tcdiff_mjpeg.h")
 HEADER_FOOTLOCK = os.path.join(os.path.dirname(HEADER), "tcdiff_footlock.h")
 HEADER_GROUP = os.path.join(os.path.dirname(HEADER), "tcdiff_group.h")
 HEADER_APART = os.path.join(os.path.dirname(HEADER), "tcdiff_apart.h")
+HEADER_GROUND = os.path.join(os.path.dirname(HEADER), "tcdiff_ground.h")
 
 
 class TcdiffError(RuntimeError):
@@ -198,3 +199,10 @@ def load_apart() -> Abi:
     tcdiff_*, tcx_*, tcs_*, tcr_*, tcj_*, tck_* and tcg_* are frozen"""
     with open(HEADER_APART) as f:
         return parse(f.read(), "include/tcdiff_apart.h", prefix="tcp_")
+
+
+def load_ground() -> Abi:
+    """the tenth header: putting the dancers on the floor, tcf_ground_workspace, tcf_ground_metrics and tcf_ground, and its constants;
+    tcf_* because tcdiff_*, tcx_*, tcs_*, tcr_*, tcj_*, tck_*, tcg_* and tcp_* are frozen"""
+    with open(HEADER_GROUND) as f:
+        return parse(f.read(), "include/tcdiff_ground.h", prefix="tcf_")

@@ -695,6 +695,7 @@ class GaussianDiffusion(nn.Module):
     draw_audio_folder = None     # where the clips' .wav files are looked up by basename; None: beside the names
     foot_lock = False            # True: render_sample pins the planted feet (tcdiff_amd/footlock.py) before anything is written
     keep_apart = False           # True: render_sample first shifts the roots so that the bodies do not touch (tcdiff_amd/apart.py)
+    ground = False               # True / a number: render_sample then shifts the roots vertically onto the estimated / that floor (tcdiff_amd/ground.py)
 
     @torch.no_grad()
     def render_sample(self, shape, cond, normalizer=None, epoch=None, render_out=None, fk_out=None, name=None,
@@ -732,6 +733,10 @@ class GaussianDiffusion(nn.Module):
         With ``self.keep_apart = True`` (likewise an attribute, False by default) ``keep_apart`` runs first, right after the export
         (tcdiff_amd/apart.py: the roots shifted horizontally so that the dancers' bodies do not touch), and the foot lock and every
         writer get the shifted ``pos`` and joints; with it False nothing changes.
+        With ``self.ground = True`` (likewise an attribute, False by default) ``ground`` runs after ``keep_apart`` and before the
+        foot lock (tcdiff_amd/ground.py: the roots shifted vertically so that the planted feet stand on the floor estimated from them
+        and no part of a body sinks below it), so that the lock pins feet that already stand on the floor; a number instead of True is
+        the floor's height.  The foot lock and every writer get the shifted ``pos`` and joints; with it False nothing changes.
         The samples are returned either way (the reference returns None)."""
         if self.draw_format not in ("png", "avi"):
             raise L.TcdiffError(f'render_sample: draw_format must be "png" or "avi", got {self.draw_format!r}')
@@ -748,6 +753,10 @@ class GaussianDiffusion(nn.Module):
             if self.keep_apart:          # before the foot lock: a shifted root slides a planted foot, and the lock re-pins it
                 from .apart import keep_apart
                 pos, poses = keep_apart(pos, poses, dn=int(required_dancer_num), parents=parents)[:2]
+            if self.ground is not False and self.ground is not None:          # after keep_apart, before the foot lock: the lock then pins feet on the floor
+                from .ground import ground
+                level = None if self.ground is True else self.ground
+                pos, poses = ground(pos, poses, contacts, dn=int(required_dancer_num), floor=level, parents=parents)[:2]
             if self.foot_lock:
                 from .footlock import foot_lock
                 locked = foot_lock(q, pos, contacts, dn=int(required_dancer_num), parents=parents, offsets=offsets)

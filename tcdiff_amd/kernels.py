@@ -821,3 +821,35 @@ def keep_apart(pos, joints, up, parents, radii, mobility, margin, iterations, ro
                                     0 if workspace is None else workspace.numel() * workspace.element_size(), _p(pos_out), _p(joints_out),
                                     _p(shift), _p(contact_before), _p(contact_after), _p(gap_min_before), _p(gap_min_after), _p(pushed),
                                     _p(capped), _p(max_shift), _p(max_step), stream()), "tcp_keep_apart")
+
+
+# ---- putting the dancers on the floor (include/tcdiff_ground.h) ----------------------------------------------------------------
+def ground_workspace(b, dn, T) -> int:
+    """the bytes of workspace ground and ground_metrics need"""
+    n = C.c_long(0)
+    L.check(L.load().tcf_ground_workspace(b, dn, T, C.byref(n)), "tcf_ground_workspace")
+    return n.value
+
+
+def ground_metrics(joints, contacts, up, parents, radii, floor_in, contact_threshold, still, tolerance, workspace, floor, counts, values):
+    """joints (b, dn, T, 24, 3) fp32 view and contacts (b, dn, T, 4) fp32 view or None, read by their strides; parents: 24 ints, radii:
+    24 floats (host); floor_in (b,) float64 or None; workspace: a uint8 tensor; floor (b,) float64; counts (3, b, dn) int64, values
+    (3, b, dn) float64.  Three launches, two with floor_in."""
+    b, dn, T = joints.shape[:3]
+    L.check(L.load().tcf_ground_metrics(_p(joints), _strides(joints, 3), _p(contacts), _strides(contacts, 4), b, dn, T, up,
+                                        (C.c_int * 24)(*parents), (C.c_double * 24)(*radii), _p(floor_in), contact_threshold, still, tolerance,
+                                        _p(workspace), 0 if workspace is None else workspace.numel() * workspace.element_size(), _p(floor),
+                                        _p(counts), _p(values), stream()), "tcf_ground_metrics")
+
+
+def ground(pos, joints, contacts, up, parents, radii, floor_in, contact_threshold, still, tolerance, blend, max_lift, workspace, pos_out,
+           joints_out, shift, floor, counts_before, values_before, counts_after, values_after, capped, max_shift, max_step):
+    """pos (b, T dn, 3) fp32 contiguous; joints and contacts as for ground_metrics; pos_out / joints_out contiguous; shift (b, dn, T)
+    float64 or None; floor (b,); counts_* (3, b, dn) int64, values_* (3, b, dn) float64; capped (b, dn) int64, max_shift / max_step
+    (b, dn) float64.  Five launches, four with floor_in."""
+    b, dn, T = joints.shape[:3]
+    L.check(L.load().tcf_ground(_p(pos), _p(joints), _strides(joints, 3), _p(contacts), _strides(contacts, 4), b, dn, T, up,
+                                (C.c_int * 24)(*parents), (C.c_double * 24)(*radii), _p(floor_in), contact_threshold, still, tolerance, blend,
+                                max_lift, _p(workspace), 0 if workspace is None else workspace.numel() * workspace.element_size(), _p(pos_out),
+                                _p(joints_out), _p(shift), _p(floor), _p(counts_before), _p(values_before), _p(counts_after),
+                                _p(values_after), _p(capped), _p(max_shift), _p(max_step), stream()), "tcf_ground")
