@@ -2,7 +2,8 @@
 include/tcdiff_hip_ext.h, the launchers added since the first header was pinned, is read the same way (load_ext), and so is
 include/tcdiff_gltf.h, whose function carries the prefix tcx_ (load_gltf), include/tcdiff_skin.h, prefix tcs_ (load_skin), include/tcdiff_shade.h,
 prefix tcr_ (load_shade), include/tcdiff_mjpeg.h, prefix tcj_ (load_mjpeg), include/tcdiff_footlock.h, prefix tck_ (load_footlock), include/tcdiff_group.h, prefix tcg_ (load_group),
-include/tcdiff_apart.h, prefix tcp_ (load_apart), and include/tcdiff_ground.h, prefix tcf_ (load_ground).
+include/tcdiff_apart.h, prefix tcp_ (load_apart), include/tcdiff_ground.h, prefix tcf_ (load_ground), and include/tcdiff_meshcontact.h, prefix
+tcm_ (load_meshcontact).
 
 The headers are the one place where the ABI is written down; _lib.py binds the library from what parse() returns.  The parser
 knows the C that the header uses and nothing more, and it never guesses: a declaration it does not recognise raises
@@ -23,6 +24,7 @@ HEADER_FOOTLOCK = os.path.join(os.path.dirname(HEADER), "tcdiff_footlock.h")
 HEADER_GROUP = os.path.join(os.path.dirname(HEADER), "tcdiff_group.h")
 HEADER_APART = os.path.join(os.path.dirname(HEADER), "tcdiff_apart.h")
 HEADER_GROUND = os.path.join(os.path.dirname(HEADER), "tcdiff_ground.h")
+HEADER_MESHCONTACT = os.path.join(os.path.dirname(HEADER), "tcdiff_meshcontact.h")
 
 
 class TcdiffError(RuntimeError):
@@ -206,3 +208,10 @@ def load_ground() -> Abi:
     tcf_* because tcdiff_*, tcx_*, tcs_*, tcr_*, tcj_*, tck_*, tcg_* and tcp_* are frozen"""
     with open(HEADER_GROUND) as f:
         return parse(f.read(), "include/tcdiff_ground.h", prefix="tcf_")
+
+
+def load_meshcontact() -> Abi:
+    """the eleventh header: mesh-level contact between the skinned bodies, tcm_mesh_contact_workspace and tcm_mesh_contact, and its
+    constants; tcm_* because tcdiff_*, tcx_*, tcs_*, tcr_*, tcj_*, tck_*, tcg_*, tcp_* and tcf_* are frozen"""
+    with open(HEADER_MESHCONTACT) as f:
+        return parse(f.read(), "include/tcdiff_meshcontact.h", prefix="tcm_")

@@ -135,6 +135,20 @@ def _integers(a, key) -> np.ndarray:
     return a.astype(np.int64)
 
 
+def faces_closed(faces) -> bool:
+    """(F, 3) whole numbers >= 0 -> True iff every directed edge of the faces occurs once and its reverse once (an edge from a
+    vertex to itself never does)"""
+    f = np.asarray(faces, np.int64).reshape(-1, 3)
+    tail, head = f.reshape(-1), f[:, [1, 2, 0]].reshape(-1)
+    if (tail == head).any():
+        return False
+    n = int(f.max()) + 1
+    edges, counts = np.unique(tail * n + head, return_counts=True)
+    if (counts != 1).any():
+        return False
+    return bool(np.array_equal(edges, np.unique(head * n + tail)))
+
+
 class BodyModel:
     """What ``load_body_model`` returns: the float64 host arrays (``build_glb`` reads them) and, per device, the float32 images
     the kernels read, made on first use.
@@ -150,6 +164,7 @@ class BodyModel:
         self._parents_c = (C.c_int * 24)(*parents)
         self._images = {}
         self._adjacency = None
+        self._closed = None
         for a in (v_shaped, J, offsets, blend, weights, weight_values, weight_joints, faces, betas):
             a.setflags(write=False)
 
@@ -167,6 +182,13 @@ class BodyModel:
             listed.setflags(write=False)
             self._adjacency = (start, listed)
         return self._adjacency
+
+    def closed(self) -> bool:
+        """Is the mesh a closed, consistently wound surface: does every directed edge (i -> j of a face) occur exactly once, and its
+        reverse exactly once?  On the host with numpy, once, cached; what ``mesh_contact`` asks before it counts rays."""
+        if self._closed is None:
+            self._closed = faces_closed(self.faces)
+        return self._closed
 
     def images(self, device) -> dict:
         """the float32 device images, each float64 array rounded once: v_shaped, blend, J, offsets, weights (V, K), joints (V, K) int32;

@@ -853,3 +853,23 @@ def ground(pos, joints, contacts, up, parents, radii, floor_in, contact_threshol
                                 max_lift, _p(workspace), 0 if workspace is None else workspace.numel() * workspace.element_size(), _p(pos_out),
                                 _p(joints_out), _p(shift), _p(floor), _p(counts_before), _p(values_before), _p(counts_after),
                                 _p(values_after), _p(capped), _p(max_shift), _p(max_step), stream()), "tcf_ground")
+
+
+# ---- mesh-level contact between the skinned bodies (include/tcdiff_meshcontact.h) ----------------------------------------------------
+def mesh_contact_workspace(b, dn, T, V, F) -> int:
+    """the bytes of workspace mesh_contact needs"""
+    n = C.c_long(0)
+    L.check(L.load().tcm_mesh_contact_workspace(b, dn, T, V, F, C.byref(n)), "tcm_mesh_contact_workspace")
+    return n.value
+
+
+def mesh_contact(vertices, faces, faces_host, dn, up, workspace, inside, depth, rate, episodes, depth_max, deepest, inside_mean):
+    """vertices (b, T dn, V, 3) fp32 view, read by its two leading strides; faces (F, 3) int32 on the device and faces_host, the same
+    as a contiguous int32 numpy array; workspace: a uint8 tensor; inside (b, P, T, 2) int32 and depth (b, P, T) float64 or None; rate,
+    depth_max, inside_mean (b, P) float64; episodes (b, P) and deepest (b, P, 3) int64.  Three launches, none with one dancer."""
+    b, rows, V = vertices.shape[:3]
+    F = faces_host.shape[0]
+    L.check(L.load().tcm_mesh_contact(_p(vertices), _strides(vertices, 2), _p(faces), faces_host.ctypes.data, b, dn, rows // dn,
+                                      V, F, up, _p(workspace), 0 if workspace is None else workspace.numel() * workspace.element_size(),
+                                      _p(inside), _p(depth), _p(rate), _p(episodes), _p(depth_max), _p(deepest), _p(inside_mean), stream()),
+            "tcm_mesh_contact")
