@@ -11,8 +11,8 @@ clips and reports what it did (``pushed``, ``max_shift``, ``max_step``) and what
 The reference has no counterpart: it renders the raw poses.  The construction is the project's own; parity with any other tool is
 unpinned.  ``margin``, ``iterations``, ``rounds``, ``blend`` and ``max_push`` are choices, not measurements.  Not promised: with three
 or more dancers a push that clears one pair can close another; rounds reduce that but need not end it.  Not built: vertical moves,
-changing a pose to dodge, resolving inside the sampler, mesh-level contact, contact between parts of one dancer, smoothing beyond
-the envelope.
+changing a pose to dodge, resolving inside the sampler, mesh-level contact, resolving a contact between parts of one dancer
+(``self_contact``, tcdiff_amd/self_contact.py, measures it), smoothing beyond the envelope.
 """
 from __future__ import annotations
 

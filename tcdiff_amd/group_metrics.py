@@ -13,8 +13,9 @@
 
 include/tcdiff_group.h is the definition.  The metrics are the project's own, in the spirit of AIOZ-GDance's TIF and GMC; parity with
 AIOZ-GDance's code is unpinned.  The radii, the window, the lag range and ``sigma_floor`` are choices, not measurements.  Not built:
-GMR (it needs a trained feature extractor), contact between parts of one dancer, drawing a contact.  Resolving one is ``keep_apart``
-(tcdiff_amd/apart.py); the surfaces themselves are measured by ``mesh_contact`` (tcdiff_amd/mesh_contact.py).
+GMR (it needs a trained feature extractor), drawing a contact.  Resolving one is ``keep_apart`` (tcdiff_amd/apart.py); the surfaces
+themselves are measured by ``mesh_contact`` (tcdiff_amd/mesh_contact.py); contact between parts of one dancer is ``self_contact``
+(tcdiff_amd/self_contact.py).
 """
 from __future__ import annotations
 

@@ -873,3 +873,24 @@ def mesh_contact(vertices, faces, faces_host, dn, up, workspace, inside, depth, 
                                       V, F, up, _p(workspace), 0 if workspace is None else workspace.numel() * workspace.element_size(),
                                       _p(inside), _p(depth), _p(rate), _p(episodes), _p(depth_max), _p(deepest), _p(inside_mean), stream()),
             "tcm_mesh_contact")
+
+
+# ---- a dancer's contact with itself (include/tcdiff_selfcontact.h) ---------------------------------------------------------------
+def self_contact_workspace(b, dn, T) -> int:
+    """the bytes of workspace self_contact needs"""
+    n = C.c_long(0)
+    L.check(L.load().tci_self_contact_workspace(b, dn, T, C.byref(n)), "tci_self_contact_workspace")
+    return n.value
+
+
+def self_contact(joints, parents, radii, mask, tolerance, workspace, gap, closest, rate, gap_min, episodes, closest_min, depth_mean,
+                 pair_frames):
+    """joints (b, dn, T, 24, 3) fp32 view, read by its strides; parents: 24 ints, radii: 24 floats, mask: four 64-bit words (host);
+    workspace: a uint8 tensor; gap (b, dn, T) float64 / closest (b, dn, T) int32 contiguous or None; rate, gap_min, depth_mean (b, dn)
+    float64; episodes (b, dn), closest_min (b, dn, 3) and pair_frames (b, dn, 253) int64.  Two launches."""
+    b, dn, T = joints.shape[:3]
+    L.check(L.load().tci_self_contact(_p(joints), _strides(joints, 3), b, dn, T, (C.c_int * 24)(*parents), (C.c_double * 24)(*radii),
+                                      (C.c_uint64 * 4)(*mask), tolerance, _p(workspace),
+                                      0 if workspace is None else workspace.numel() * workspace.element_size(), _p(gap), _p(closest),
+                                      _p(rate), _p(gap_min), _p(episodes), _p(closest_min), _p(depth_mean), _p(pair_frames), stream()),
+            "tci_self_contact")

@@ -11,9 +11,9 @@ pair of dancers, in three launches (``tcm_mesh_contact``, csrc/meshcontact.hip),
     print(summarize(mesh_contact(body, skin(body, q, pos), dn)))
 
 include/tcdiff_meshcontact.h is the definition.  The construction is the textbook one, restated; parity with any other tool is
-unpinned.  Not built: edge-edge crossings between vertices (a limb thinner than the vertex spacing can pass unseen), contact of a
-dancer with itself, the gap between surfaces that do not touch, using any of this inside ``keep_apart`` or ``ground``, a penetration
-volume, a spatial hierarchy.
+unpinned.  Not built: edge-edge crossings between vertices (a limb thinner than the vertex spacing can pass unseen), mesh-level
+contact of a dancer with itself (``self_contact``, tcdiff_amd/self_contact.py, measures it on the capsules), the gap between surfaces
+that do not touch, using any of this inside ``keep_apart`` or ``ground``, a penetration volume, a spatial hierarchy.
 """
 from __future__ import annotations
 
