@@ -696,6 +696,7 @@ class GaussianDiffusion(nn.Module):
     foot_lock = False            # True: render_sample pins the planted feet (tcdiff_amd/footlock.py) before anything is written
     keep_apart = False           # True: render_sample first shifts the roots so that the bodies do not touch (tcdiff_amd/apart.py)
     ground = False               # True / a number: render_sample then shifts the roots vertically onto the estimated / that floor (tcdiff_amd/ground.py)
+    smooth = False               # True / an odd window: render_sample first of all filters the jitter out of the exported poses (tcdiff_amd/smooth.py)
 
     @torch.no_grad()
     def render_sample(self, shape, cond, normalizer=None, epoch=None, render_out=None, fk_out=None, name=None,
@@ -737,6 +738,12 @@ class GaussianDiffusion(nn.Module):
         foot lock (tcdiff_amd/ground.py: the roots shifted vertically so that the planted feet stand on the floor estimated from them
         and no part of a body sinks below it), so that the lock pins feet that already stand on the floor; a number instead of True is
         the floor's height.  The foot lock and every writer get the shifted ``pos`` and joints; with it False nothing changes.
+        With ``self.smooth = True`` (likewise an attribute, False by default) ``smooth`` runs first of all, right after the export
+        and before ``keep_apart`` (tcdiff_amd/smooth.py: a Savitzky-Golay filter of the root positions and, through unit
+        quaternions, of the rotations, against the frame-to-frame jitter of the sampler's independent rows), so that the three
+        correctors act on the filtered joints and each keeps its promise on the output; an odd integer instead of True is the
+        window.  ``keep_apart``, ``ground``, the foot lock and every writer get the filtered ``q``, ``pos`` and joints; with it False
+        nothing changes.
         The samples are returned either way (the reference returns None)."""
         if self.draw_format not in ("png", "avi"):
             raise L.TcdiffError(f'render_sample: draw_format must be "png" or "avi", got {self.draw_format!r}')
@@ -750,6 +757,11 @@ class GaussianDiffusion(nn.Module):
             x = samples if samples.is_cuda else samples.to(self._device())
             parents, offsets = self._skeleton(x.device)
             q, pos, poses, contacts = export_poses(x, normalizer, mode, required_dancer_num, parents=parents, offsets=offsets)
+            smooth_by = getattr(self, "smooth", False)
+            if smooth_by is not False and smooth_by is not None:          # first of all: the correctors below act on the filtered joints
+                from .smooth import smooth
+                kw = {} if smooth_by is True else dict(window=smooth_by)
+                q, pos, poses = smooth(q, pos, dn=int(required_dancer_num), parents=parents, offsets=offsets, measure=False, **kw)[:3]
             if self.keep_apart:          # before the foot lock: a shifted root slides a planted foot, and the lock re-pins it
                 from .apart import keep_apart
                 pos, poses = keep_apart(pos, poses, dn=int(required_dancer_num), parents=parents)[:2]

@@ -894,3 +894,31 @@ def self_contact(joints, parents, radii, mask, tolerance, workspace, gap, closes
                                       0 if workspace is None else workspace.numel() * workspace.element_size(), _p(gap), _p(closest),
                                       _p(rate), _p(gap_min), _p(episodes), _p(closest_min), _p(depth_mean), _p(pair_frames), stream()),
             "tci_self_contact")
+
+
+# ---- the jitter scores and the rotation filter (include/tcdiff_smooth.h) -----------------------------------------------------------
+def smoothness(joints, fps, accel_mean, jitter, jitter_local, root_jitter, accel_max, jitter_max, accel_peak, jitter_peak, terms):
+    """joints (b, dn, T, 24, 3) fp32 view, read by its strides; the six (b, dn) float64 outputs, accel_peak / jitter_peak (b, dn, 2) and
+    terms (b, dn) int32.  One launch."""
+    b, dn, T = joints.shape[:3]
+    L.check(L.load().tcw_smoothness(_p(joints), _strides(joints, 3), b, dn, T, fps, _p(accel_mean), _p(jitter), _p(jitter_local),
+                                    _p(root_jitter), _p(accel_max), _p(jitter_max), _p(accel_peak), _p(jitter_peak), _p(terms), stream()),
+            "tcw_smoothness")
+
+
+def smooth_workspace(b, dn, T) -> int:
+    """the bytes of workspace smooth needs"""
+    n = C.c_long(0)
+    L.check(L.load().tcw_smooth_workspace(b, dn, T, C.byref(n)), "tcw_smooth_workspace")
+    return n.value
+
+
+def smooth(q, pos, b, dn, T, window, taps, root_window, root_taps, joints_mask, parents, offsets, workspace, q_out, pos_out, joints, joints_in,
+           max_rot_change, max_pos_change, copied):
+    """q (b, T dn, 24, 3) / pos (b, T dn, 3) fp32 contiguous; taps (window, window) / root_taps (root_window, root_window) float64 on the
+    device; joints_mask: 24 bits; workspace: a uint8 tensor; q_out / pos_out like q / pos; joints, joints_in (b, dn, T, 24, 3) or None;
+    max_rot_change, max_pos_change (b, dn) float64; copied (b, dn) int32.  Two launches."""
+    L.check(L.load().tcw_smooth(_p(q), _p(pos), b, dn, T, window, _p(taps), root_window, _p(root_taps), joints_mask,
+                                *_skeleton(parents, offsets), _p(workspace),
+                                0 if workspace is None else workspace.numel() * workspace.element_size(), _p(q_out), _p(pos_out), _p(joints),
+                                _p(joints_in), _p(max_rot_change), _p(max_pos_change), _p(copied), stream()), "tcw_smooth")
