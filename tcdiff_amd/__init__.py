@@ -25,6 +25,7 @@ from .ground import Ground, ground, ground_metrics  # noqa: F401
 from .mesh_contact import mesh_contact, evaluate_mesh_contact  # noqa: F401
 from .self_contact import self_contact, self_pairs, pair_index, pair_of, pair_mask, evaluate_self_contact  # noqa: F401
 from .smooth import Smooth, smooth, smoothness, evaluate_smoothness, savgol_table  # noqa: F401
+from .choreo import Plan, plan, trajectory_error, formation  # noqa: F401
 from .audio import WavData, read_wav, decode, resample, slice_audio, load_audio  # noqa: F401
 
 __all__ = ["DanceDecoder", "GaussianDiffusion", "EMA", "Adan", "SMPLSkeleton", "ax_from_6v", "TrajDecoder", "TrajTrainer", "TrajAdamW",
@@ -38,4 +39,5 @@ __all__ = ["DanceDecoder", "GaussianDiffusion", "EMA", "Adan", "SMPLSkeleton", "
            "group_metrics", "pairs", "capsule_radii", "radii_from_body", "evaluate_group", "Apart", "keep_apart",
            "Ground", "ground", "ground_metrics", "mesh_contact", "evaluate_mesh_contact",
            "self_contact", "self_pairs", "pair_index", "pair_of", "pair_mask", "evaluate_self_contact",
-           "Smooth", "smooth", "smoothness", "evaluate_smoothness", "savgol_table"]
+           "Smooth", "smooth", "smoothness", "evaluate_smoothness", "savgol_table",
+           "Plan", "plan", "trajectory_error", "formation"]

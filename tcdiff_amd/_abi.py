@@ -3,8 +3,8 @@ include/tcdiff_hip_ext.h, the launchers added since the first header was pinned,
 include/tcdiff_gltf.h, whose function carries the prefix tcx_ (load_gltf), include/tcdiff_skin.h, prefix tcs_ (load_skin), include/tcdiff_shade.h,
 prefix tcr_ (load_shade), include/tcdiff_mjpeg.h, prefix tcj_ (load_mjpeg), include/tcdiff_footlock.h, prefix tck_ (load_footlock), include/tcdiff_group.h, prefix tcg_ (load_group),
 include/tcdiff_apart.h, prefix tcp_ (load_apart), include/tcdiff_ground.h, prefix tcf_ (load_ground), include/tcdiff_meshcontact.h, prefix
-tcm_ (load_meshcontact), include/tcdiff_selfcontact.h, prefix tci_ (load_selfcontact), and include/tcdiff_smooth.h, prefix tcw_
-(load_smooth).
+tcm_ (load_meshcontact), include/tcdiff_selfcontact.h, prefix tci_ (load_selfcontact), include/tcdiff_smooth.h, prefix tcw_
+(load_smooth), and include/tcdiff_choreo.h, prefix tcc_ (load_choreo).
 
 The headers are the one place where the ABI is written down; _lib.py binds the library from what parse() returns.  The parser
 knows the C that the header uses and nothing more, and it never guesses: a declaration it does not recognise raises
@@ -28,6 +28,7 @@ HEADER_GROUND = os.path.join(os.path.dirname(HEADER), "tcdiff_ground.h")
 HEADER_MESHCONTACT = os.path.join(os.path.dirname(HEADER), "tcdiff_meshcontact.h")
 HEADER_SELFCONTACT = os.path.join(os.path.dirname(HEADER), "tcdiff_selfcontact.h")
 HEADER_SMOOTH = os.path.join(os.path.dirname(HEADER), "tcdiff_smooth.h")
+HEADER_CHOREO = os.path.join(os.path.dirname(HEADER), "tcdiff_choreo.h")
 
 
 class TcdiffError(RuntimeError):
@@ -232,3 +233,10 @@ def load_smooth() -> Abi:
     constants; tcw_* because tcdiff_*, tcx_*, tcs_*, tcr_*, tcj_*, tck_*, tcg_*, tcp_*, tcf_*, tcm_* and tci_* are frozen"""
     with open(HEADER_SMOOTH) as f:
         return parse(f.read(), "include/tcdiff_smooth.h", prefix="tcw_")
+
+
+def load_choreo() -> Abi:
+    """the fourteenth header: the choreography planner and its closing check, tcc_plan and tcc_trajectory_error, and its constants;
+    tcc_* because tcdiff_*, tcx_*, tcs_*, tcr_*, tcj_*, tck_*, tcg_*, tcp_*, tcf_*, tcm_*, tci_* and tcw_* are frozen"""
+    with open(HEADER_CHOREO) as f:
+        return parse(f.read(), "include/tcdiff_choreo.h", prefix="tcc_")

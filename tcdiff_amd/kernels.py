@@ -922,3 +922,24 @@ def smooth(q, pos, b, dn, T, window, taps, root_window, root_taps, joints_mask, 
                                 *_skeleton(parents, offsets), _p(workspace),
                                 0 if workspace is None else workspace.numel() * workspace.element_size(), _p(q_out), _p(pos_out), _p(joints),
                                 _p(joints_in), _p(max_rot_change), _p(max_pos_change), _p(copied), stream()), "tcw_smooth")
+
+
+# ---- the choreography planner and its closing check (include/tcdiff_choreo.h) -----------------------------------------------------
+def choreo_plan(points, keys, counts, frames, fps, scale, min_, min_distance, max_speed, traj, x0, status, clamped, speed_max, speed_peak,
+                too_fast, path_length, dist_min, dist_min_frame, too_close):
+    """points (b, dn, K, 2) fp32 contiguous; keys (K,) or (b, dn, K) int32; counts (b, dn) int32 or None; scale / min_: two HOST floats
+    each or None; traj (b, dn, frames, 2), x0 (b, frames dn, 3) fp32; the per-dancer reports (b, dn), the per-pair reports
+    (b, dn (dn - 1) / 2) (None with one dancer).  Two launches, one with one dancer."""
+    b, dn, K, _ = points.shape
+    norm = (None, None) if scale is None else ((C.c_float * 2)(*scale), (C.c_float * 2)(*min_))
+    L.check(L.load().tcc_plan(_p(points), _p(keys), int(keys.dim() == 3), _p(counts), b, dn, K, frames, fps, norm[0], norm[1], min_distance,
+                              max_speed, _p(traj), _p(x0), _p(status), _p(clamped), _p(speed_max), _p(speed_peak), _p(too_fast),
+                              _p(path_length), _p(dist_min), _p(dist_min_frame), _p(too_close), stream()), "tcc_plan")
+
+
+def trajectory_error(joints, traj, up, err_mean, err_max, err_final, err_peak, counted):
+    """joints (b, dn, T, 24, 3) fp32 view, read by its strides; traj (b, dn, T, 2) fp32 contiguous; err_mean, err_max, err_final (b, dn)
+    float64; err_peak, counted (b, dn) int32.  One launch."""
+    b, dn, T = joints.shape[:3]
+    L.check(L.load().tcc_trajectory_error(_p(joints), _strides(joints, 3), _p(traj), b, dn, T, up, _p(err_mean), _p(err_max), _p(err_final),
+                                          _p(err_peak), _p(counted), stream()), "tcc_trajectory_error")
