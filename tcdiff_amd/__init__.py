@@ -26,6 +26,7 @@ from .mesh_contact import mesh_contact, evaluate_mesh_contact  # noqa: F401
 from .self_contact import self_contact, self_pairs, pair_index, pair_of, pair_mask, evaluate_self_contact  # noqa: F401
 from .smooth import Smooth, smooth, smoothness, evaluate_smoothness, savgol_table  # noqa: F401
 from .choreo import Plan, plan, trajectory_error, formation  # noqa: F401
+from .beat_sync import BeatSync, beat_sync, motion_beats, gaussian_table  # noqa: F401
 from .audio import WavData, read_wav, decode, resample, slice_audio, load_audio  # noqa: F401
 
 __all__ = ["DanceDecoder", "GaussianDiffusion", "EMA", "Adan", "SMPLSkeleton", "ax_from_6v", "TrajDecoder", "TrajTrainer", "TrajAdamW",
@@ -40,4 +41,5 @@ __all__ = ["DanceDecoder", "GaussianDiffusion", "EMA", "Adan", "SMPLSkeleton", "
            "Ground", "ground", "ground_metrics", "mesh_contact", "evaluate_mesh_contact",
            "self_contact", "self_pairs", "pair_index", "pair_of", "pair_mask", "evaluate_self_contact",
            "Smooth", "smooth", "smoothness", "evaluate_smoothness", "savgol_table",
-           "Plan", "plan", "trajectory_error", "formation"]
+           "Plan", "plan", "trajectory_error", "formation",
+           "BeatSync", "beat_sync", "motion_beats", "gaussian_table"]

@@ -4,7 +4,7 @@ include/tcdiff_gltf.h, whose function carries the prefix tcx_ (load_gltf), inclu
 prefix tcr_ (load_shade), include/tcdiff_mjpeg.h, prefix tcj_ (load_mjpeg), include/tcdiff_footlock.h, prefix tck_ (load_footlock), include/tcdiff_group.h, prefix tcg_ (load_group),
 include/tcdiff_apart.h, prefix tcp_ (load_apart), include/tcdiff_ground.h, prefix tcf_ (load_ground), include/tcdiff_meshcontact.h, prefix
 tcm_ (load_meshcontact), include/tcdiff_selfcontact.h, prefix tci_ (load_selfcontact), include/tcdiff_smooth.h, prefix tcw_
-(load_smooth), and include/tcdiff_choreo.h, prefix tcc_ (load_choreo).
+(load_smooth), include/tcdiff_choreo.h, prefix tcc_ (load_choreo), and include/tcdiff_beatsync.h, prefix tcb_ (load_beatsync).
 
 The headers are the one place where the ABI is written down; _lib.py binds the library from what parse() returns.  The parser
 knows the C that the header uses and nothing more, and it never guesses: a declaration it does not recognise raises
@@ -29,6 +29,7 @@ HEADER_MESHCONTACT = os.path.join(os.path.dirname(HEADER), "tcdiff_meshcontact.h
 HEADER_SELFCONTACT = os.path.join(os.path.dirname(HEADER), "tcdiff_selfcontact.h")
 HEADER_SMOOTH = os.path.join(os.path.dirname(HEADER), "tcdiff_smooth.h")
 HEADER_CHOREO = os.path.join(os.path.dirname(HEADER), "tcdiff_choreo.h")
+HEADER_BEATSYNC = os.path.join(os.path.dirname(HEADER), "tcdiff_beatsync.h")
 
 
 class TcdiffError(RuntimeError):
@@ -240,3 +241,11 @@ def load_choreo() -> Abi:
     tcc_* because tcdiff_*, tcx_*, tcs_*, tcr_*, tcj_*, tck_*, tcg_*, tcp_*, tcf_*, tcm_*, tci_* and tcw_* are frozen"""
     with open(HEADER_CHOREO) as f:
         return parse(f.read(), "include/tcdiff_choreo.h", prefix="tcc_")
+
+
+def load_beatsync() -> Abi:
+    """the fifteenth header: the kinematic beats and the time warp onto the music's, tcb_motion_beats, tcb_beat_sync and
+    tcb_beat_sync_workspace, and its constants; tcb_* because tcdiff_*, tcx_*, tcs_*, tcr_*, tcj_*, tck_*, tcg_*, tcp_*, tcf_*, tcm_*,
+    tci_*, tcw_* and tcc_* are frozen"""
+    with open(HEADER_BEATSYNC) as f:
+        return parse(f.read(), "include/tcdiff_beatsync.h", prefix="tcb_")

@@ -1,6 +1,7 @@
 """ctypes binding of libtcdiff_gfx950.so (include/tcdiff_hip.h, include/tcdiff_hip_ext.h, include/tcdiff_gltf.h, include/tcdiff_skin.h
 include/tcdiff_shade.h, include/tcdiff_mjpeg.h, include/tcdiff_footlock.h, include/tcdiff_group.h, include/tcdiff_apart.h,
-include/tcdiff_ground.h, include/tcdiff_meshcontact.h, include/tcdiff_selfcontact.h, include/tcdiff_smooth.h and include/tcdiff_choreo.h).
+include/tcdiff_ground.h, include/tcdiff_meshcontact.h, include/tcdiff_selfcontact.h, include/tcdiff_smooth.h, include/tcdiff_choreo.h and
+include/tcdiff_beatsync.h).
 
 The product path has NO fallback: if the shared library is missing or a launcher returns an error, this
 module raises.  Nothing here touches ``oracle/``.
@@ -28,6 +29,7 @@ MESH = _abi.load_meshcontact()                       # the eleventh: tcm_mesh_co
 SELF = _abi.load_selfcontact()                       # the twelfth: tci_self_contact_workspace, tci_self_contact and their constants, likewise
 SMOOTH = _abi.load_smooth()                          # the thirteenth: tcw_smoothness, tcw_smooth_workspace, tcw_smooth and their constants, likewise
 CHOREO = _abi.load_choreo()                          # the fourteenth: tcc_plan, tcc_trajectory_error and their constants, likewise
+BEATSYNC = _abi.load_beatsync()                      # the fifteenth: tcb_beat_sync_workspace, tcb_motion_beats, tcb_beat_sync and their constants, likewise
 
 for _name, _value in {**ABI.constants, **EXT.constants}.items():          # TC_X -> X, TC_DTYPE_X -> DT_X
     globals()["DT_" + _name[9:] if _name.startswith("TC_DTYPE_") else _name[3:]] = _value
@@ -82,7 +84,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (restype, argtypes, _) in {**ABI.functions, **EXT.functions, **GLTF.functions, **SKIN.functions, **SHADE.functions, **MJPEG.functions, **FOOTLOCK.functions,
                                             **GROUP.functions, **APART.functions, **GROUND.functions, **MESH.functions, **SELF.functions,
-                                            **SMOOTH.functions, **CHOREO.functions}.items():
+                                            **SMOOTH.functions, **CHOREO.functions, **BEATSYNC.functions}.items():
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = argtypes, restype
     _lib = lib

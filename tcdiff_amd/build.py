@@ -10,9 +10,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = [os.path.join(HERE, "csrc", f) for f in ("gemm.hip", "attention.hip", "ops.hip", "chain.hip", "train.hip", "train_ops.hip",
                                                "attention_train.hip", "gemm_rows.hip", "chain_split.hip", "export.hip", "navigator.hip", "navigator_train.hip", "navigator_step.hip",
-                                               "ingest.hip", "handoff.hip", "metrics.hip", "draw.hip", "set_metrics.hip", "music.hip", "beat.hip", "chroma.hip", "audio.hip", "geometric.hip", "gltf.hip", "skin.hip", "shade.hip", "mjpeg.hip", "footlock.hip", "group.hip", "apart.hip", "ground.hip", "meshcontact.hip", "selfcontact.hip", "smooth.hip", "choreo.hip")]
+                                               "ingest.hip", "handoff.hip", "metrics.hip", "draw.hip", "set_metrics.hip", "music.hip", "beat.hip", "chroma.hip", "audio.hip", "geometric.hip", "gltf.hip", "skin.hip", "shade.hip", "mjpeg.hip", "footlock.hip", "group.hip", "apart.hip", "ground.hip", "meshcontact.hip", "selfcontact.hip", "smooth.hip", "choreo.hip", "beatsync.hip")]
 HDR = sorted(os.path.join(HERE, "csrc", h) for h in os.listdir(os.path.join(HERE, "csrc")) if h.endswith(".h")) + \
-    [os.path.join(ROOT, "include", h) for h in ("tcdiff_hip.h", "tcdiff_hip_ext.h", "tcdiff_gltf.h", "tcdiff_skin.h", "tcdiff_shade.h", "tcdiff_mjpeg.h", "tcdiff_footlock.h", "tcdiff_group.h", "tcdiff_apart.h", "tcdiff_ground.h", "tcdiff_meshcontact.h", "tcdiff_selfcontact.h", "tcdiff_smooth.h", "tcdiff_choreo.h")]
+    [os.path.join(ROOT, "include", h) for h in ("tcdiff_hip.h", "tcdiff_hip_ext.h", "tcdiff_gltf.h", "tcdiff_skin.h", "tcdiff_shade.h", "tcdiff_mjpeg.h", "tcdiff_footlock.h", "tcdiff_group.h", "tcdiff_apart.h", "tcdiff_ground.h", "tcdiff_meshcontact.h", "tcdiff_selfcontact.h", "tcdiff_smooth.h", "tcdiff_choreo.h", "tcdiff_beatsync.h")]
 LIB = os.path.join(HERE, "libtcdiff_gfx950.so")
 
 

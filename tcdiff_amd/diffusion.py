@@ -697,6 +697,7 @@ class GaussianDiffusion(nn.Module):
     keep_apart = False           # True: render_sample first shifts the roots so that the bodies do not touch (tcdiff_amd/apart.py)
     ground = False               # True / a number: render_sample then shifts the roots vertically onto the estimated / that floor (tcdiff_amd/ground.py)
     smooth = False               # True / an odd window: render_sample first of all filters the jitter out of the exported poses (tcdiff_amd/smooth.py)
+    beat_sync = False            # True: render_sample before anything else retimes the exported poses onto the music's beats (tcdiff_amd/beat_sync.py)
 
     @torch.no_grad()
     def render_sample(self, shape, cond, normalizer=None, epoch=None, render_out=None, fk_out=None, name=None,
@@ -744,6 +745,11 @@ class GaussianDiffusion(nn.Module):
         correctors act on the filtered joints and each keeps its promise on the output; an odd integer instead of True is the
         window.  ``keep_apart``, ``ground``, the foot lock and every writer get the filtered ``q``, ``pos`` and joints; with it False
         nothing changes.
+        With ``self.beat_sync = True`` (likewise an attribute, False by default) ``beat_sync`` runs before all of them, right after
+        the export and before ``smooth`` (tcdiff_amd/beat_sync.py: a monotone time warp that brings the kinematic beats -- the minima
+        of the smoothed joint speed -- onto the music's beats, read from ``cond`` by ``beats_from_cond``), so that the filter takes
+        out the kinks of the resampling and the correctors and every writer act on the retimed ``q``, ``pos``, joints and contacts;
+        it needs ``cond``; with it False nothing changes.
         The samples are returned either way (the reference returns None)."""
         if self.draw_format not in ("png", "avi"):
             raise L.TcdiffError(f'render_sample: draw_format must be "png" or "avi", got {self.draw_format!r}')
@@ -757,6 +763,15 @@ class GaussianDiffusion(nn.Module):
             x = samples if samples.is_cuda else samples.to(self._device())
             parents, offsets = self._skeleton(x.device)
             q, pos, poses, contacts = export_poses(x, normalizer, mode, required_dancer_num, parents=parents, offsets=offsets)
+            if getattr(self, "beat_sync", False):          # before anything else: the filter and the correctors below act on the retimed motion
+                from .beat_sync import beat_sync
+                from .export import _is_long
+                from .metrics import beats_from_cond
+                if cond is None:
+                    raise L.TcdiffError("render_sample: beat_sync reads the music's beats from cond, got None")
+                beats = beats_from_cond(cond.to(x.device), poses.shape[2], long=_is_long(mode))
+                synced = beat_sync(q, pos, beats, dn=int(required_dancer_num), contacts=contacts, parents=parents, offsets=offsets, measure=False)
+                q, pos, poses, contacts = synced.q, synced.pos, synced.joints, synced.contacts
             smooth_by = getattr(self, "smooth", False)
             if smooth_by is not False and smooth_by is not None:          # first of all: the correctors below act on the filtered joints
                 from .smooth import smooth

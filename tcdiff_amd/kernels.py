@@ -943,3 +943,35 @@ def trajectory_error(joints, traj, up, err_mean, err_max, err_final, err_peak, c
     b, dn, T = joints.shape[:3]
     L.check(L.load().tcc_trajectory_error(_p(joints), _strides(joints, 3), _p(traj), b, dn, T, up, _p(err_mean), _p(err_max), _p(err_final),
                                           _p(err_peak), _p(counted), stream()), "tcc_trajectory_error")
+
+
+# ---- the kinematic beats and the time warp onto the music's (include/tcdiff_beatsync.h) ------------------------------------------
+def beat_sync_workspace(b, dn, T) -> int:
+    """the bytes of workspace motion_beats and beat_sync need"""
+    n = C.c_long(0)
+    L.check(L.load().tcb_beat_sync_workspace(b, dn, T, C.byref(n)), "tcb_beat_sync_workspace")
+    return n.value
+
+
+def motion_beats(joints, share, rad, weights, workspace, speed, kin, kin_count):
+    """joints (b, dn, T, 24, 3) fp32 view, read by its strides; weights (2 rad + 1,) float64 on the device; workspace: a uint8 tensor;
+    speed (b, W, T - 1) float64, kin (b, W, T) uint8, kin_count (b, W) int32, W = 1 if share else dn.  Two launches."""
+    b, dn, T = joints.shape[:3]
+    L.check(L.load().tcb_motion_beats(_p(joints), _strides(joints, 3), b, dn, T, int(share), rad, _p(weights), _p(workspace),
+                                      0 if workspace is None else workspace.numel() * workspace.element_size(), _p(speed), _p(kin),
+                                      _p(kin_count), stream()), "tcb_motion_beats")
+
+
+def beat_sync(q, pos, contacts, beats, b, dn, T, share, max_shift, max_rate, strength, rad, weights, parents, offsets, workspace, q_out, pos_out,
+              contacts_out, joints, joints_in, warp, speed, kin, status, kin_count, music_count, matched, dropped, anchors, shift_max, rate_min,
+              rate_max, rate_min_frame, rate_max_frame, moved, copied):
+    """q (b, T dn, 24, 3) / pos (b, T dn, 3) fp32 contiguous; contacts (b, dn, T, 4) fp32 contiguous or None (then contacts_out is None);
+    beats (b, T) uint8; weights (2 rad + 1,) float64 on the device; workspace: a uint8 tensor; q_out / pos_out / contacts_out like their
+    inputs; joints, joints_in (b, dn, T, 24, 3), joints_in or None; the per-warp outputs (b, W[, T]), moved / copied (b, dn).  Three
+    launches."""
+    L.check(L.load().tcb_beat_sync(_p(q), _p(pos), _p(contacts), _p(beats), b, dn, T, int(share), max_shift, max_rate, strength, rad, _p(weights),
+                                   *_skeleton(parents, offsets), _p(workspace),
+                                   0 if workspace is None else workspace.numel() * workspace.element_size(), _p(q_out), _p(pos_out),
+                                   _p(contacts_out), _p(joints), _p(joints_in), _p(warp), _p(speed), _p(kin), _p(status), _p(kin_count),
+                                   _p(music_count), _p(matched), _p(dropped), _p(anchors), _p(shift_max), _p(rate_min), _p(rate_max),
+                                   _p(rate_min_frame), _p(rate_max_frame), _p(moved), _p(copied), stream()), "tcb_beat_sync")
