@@ -694,10 +694,10 @@ class GaussianDiffusion(nn.Module):
     draw_format = "png"          # "avi": render_sample's draw_out writes Motion-JPEG AVI files (tcdiff_amd/video.py), with the clips' music if `sound`
     draw_audio_folder = None     # where the clips' .wav files are looked up by basename; None: beside the names
     foot_lock = False            # True: render_sample pins the planted feet (tcdiff_amd/footlock.py) before anything is written
-    keep_apart = False           # True: render_sample first shifts the roots so that the bodies do not touch (tcdiff_amd/apart.py)
+    keep_apart = False           # True: render_sample shifts the roots so that the bodies do not touch (tcdiff_amd/apart.py); the order: see render_sample
     ground = False               # True / a number: render_sample then shifts the roots vertically onto the estimated / that floor (tcdiff_amd/ground.py)
-    smooth = False               # True / an odd window: render_sample first of all filters the jitter out of the exported poses (tcdiff_amd/smooth.py)
-    beat_sync = False            # True: render_sample before anything else retimes the exported poses onto the music's beats (tcdiff_amd/beat_sync.py)
+    smooth = False               # True / an odd window: render_sample filters the jitter out of the exported poses (tcdiff_amd/smooth.py)
+    beat_sync = False            # True: render_sample retimes the exported poses onto the music's beats, before the four above (tcdiff_amd/beat_sync.py)
 
     @torch.no_grad()
     def render_sample(self, shape, cond, normalizer=None, epoch=None, render_out=None, fk_out=None, name=None,
@@ -729,27 +729,27 @@ class GaussianDiffusion(nn.Module):
         With a ``normalizer`` and a ``glb_out`` directory (keyword only), the exported poses are also written as animated glTF
         files (tcdiff_amd/gltf.py: the open counterpart of the reference's Blender_Visulization/ FBX conversion), one per clip with
         all its dancers, under ``fk_out``'s names with the extension .glb.  The export runs once whichever of the three asks.
-        With ``self.foot_lock = True`` (an attribute, False by default, for the same reason as ``body``) the exported poses pass
-        through ``foot_lock`` once -- the planted feet pinned, hip and knee re-solved (tcdiff_amd/footlock.py) -- and every writer
-        gets the locked ``q`` and joints in place of the raw ones; with it False nothing changes.
-        With ``self.keep_apart = True`` (likewise an attribute, False by default) ``keep_apart`` runs first, right after the export
-        (tcdiff_amd/apart.py: the roots shifted horizontally so that the dancers' bodies do not touch), and the foot lock and every
-        writer get the shifted ``pos`` and joints; with it False nothing changes.
-        With ``self.ground = True`` (likewise an attribute, False by default) ``ground`` runs after ``keep_apart`` and before the
-        foot lock (tcdiff_amd/ground.py: the roots shifted vertically so that the planted feet stand on the floor estimated from them
-        and no part of a body sinks below it), so that the lock pins feet that already stand on the floor; a number instead of True is
-        the floor's height.  The foot lock and every writer get the shifted ``pos`` and joints; with it False nothing changes.
-        With ``self.smooth = True`` (likewise an attribute, False by default) ``smooth`` runs first of all, right after the export
-        and before ``keep_apart`` (tcdiff_amd/smooth.py: a Savitzky-Golay filter of the root positions and, through unit
-        quaternions, of the rotations, against the frame-to-frame jitter of the sampler's independent rows), so that the three
-        correctors act on the filtered joints and each keeps its promise on the output; an odd integer instead of True is the
-        window.  ``keep_apart``, ``ground``, the foot lock and every writer get the filtered ``q``, ``pos`` and joints; with it False
-        nothing changes.
-        With ``self.beat_sync = True`` (likewise an attribute, False by default) ``beat_sync`` runs before all of them, right after
-        the export and before ``smooth`` (tcdiff_amd/beat_sync.py: a monotone time warp that brings the kinematic beats -- the minima
-        of the smoothed joint speed -- onto the music's beats, read from ``cond`` by ``beats_from_cond``), so that the filter takes
-        out the kinks of the resampling and the correctors and every writer act on the retimed ``q``, ``pos``, joints and contacts;
-        it needs ``cond``; with it False nothing changes.
+        Five correctors, each an attribute of this object (False by default; attributes for the same reason as ``body``), stand
+        between the export and the writers.  Those that are on run once, in this one order, each on what the one before it returned,
+        and every writer gets the last one's ``q``, ``pos``, joints and contacts; with all of them False nothing changes:
+        1. ``self.beat_sync = True``: ``beat_sync`` (tcdiff_amd/beat_sync.py: a monotone time warp that brings the kinematic beats --
+           the minima of the smoothed joint speed -- onto the music's beats, read from ``cond`` by ``beats_from_cond``; it needs
+           ``cond``) retimes ``q``, ``pos``, the joints and the contacts, so that the filter takes out the kinks of the resampling;
+        2. ``self.smooth = True``, or an odd integer, the window: ``smooth`` (tcdiff_amd/smooth.py: a Savitzky-Golay filter of the
+           root positions and, through unit quaternions, of the rotations, against the frame-to-frame jitter of the sampler's
+           independent rows) returns the filtered ``q``, ``pos`` and joints, so that the three below act on filtered joints;
+        3. ``self.keep_apart = True``: ``keep_apart`` (tcdiff_amd/apart.py: the roots shifted horizontally so that the dancers'
+           bodies do not touch) returns the shifted ``pos`` and joints; a shifted root slides a planted foot, and the lock re-pins it;
+        4. ``self.ground = True``, or a number, the floor's height: ``ground`` (tcdiff_amd/ground.py: the roots shifted vertically
+           so that the planted feet stand on the floor estimated from them and no part of a body sinks below it) returns the shifted
+           ``pos`` and joints, so that the lock pins feet that already stand on the floor;
+        5. ``self.foot_lock = True``: ``foot_lock`` (tcdiff_amd/footlock.py: the planted feet pinned, hip and knee re-solved)
+           returns the locked ``q`` and joints.
+        What each promises is measured on the end of the whole chain in tests/test_post_chain_gpu.py, on two seeded dances: every
+        planted foot stays on its anchor, and against the raw export the frames with body contact, with a body below the floor and
+        with a planted foot above it do not grow, the jitter and the mean acceleration fall and ``beat_align`` rises.  That is what
+        is measured, not a guarantee: ``keep_apart``'s shift is found frame by frame, and a deep overlap of swinging arms raised the
+        mean acceleration of the pushed dancers above the raw value (tests/test_post_chain_cpu.py).
         The samples are returned either way (the reference returns None)."""
         if self.draw_format not in ("png", "avi"):
             raise L.TcdiffError(f'render_sample: draw_format must be "png" or "avi", got {self.draw_format!r}')
@@ -773,7 +773,7 @@ class GaussianDiffusion(nn.Module):
                 synced = beat_sync(q, pos, beats, dn=int(required_dancer_num), contacts=contacts, parents=parents, offsets=offsets, measure=False)
                 q, pos, poses, contacts = synced.q, synced.pos, synced.joints, synced.contacts
             smooth_by = getattr(self, "smooth", False)
-            if smooth_by is not False and smooth_by is not None:          # first of all: the correctors below act on the filtered joints
+            if smooth_by is not False and smooth_by is not None:          # before the three correctors below: they act on the filtered joints
                 from .smooth import smooth
                 kw = {} if smooth_by is True else dict(window=smooth_by)
                 q, pos, poses = smooth(q, pos, dn=int(required_dancer_num), parents=parents, offsets=offsets, measure=False, **kw)[:3]

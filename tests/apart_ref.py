@@ -9,6 +9,9 @@ import group_ref as G
 DEFAULTS = dict(up=2, radii=None, parents=None, margin=0.02, iterations=8, rounds=3, blend=5, max_push=0.6, mobility=None)
 SMALL = 1e-18
 GUARD = 1e-9
+# the bound the GPU tests hold the float64 outputs to (tests/test_apart_gpu.py, tests/test_post_chain_gpu.py)
+MEASURED = 0.0            # metres: the largest difference of a float64 output from the restatement over every case of tests/test_apart_gpu.py (profiles/apart.txt)
+FLOAT_BOUND = min(100 * MEASURED, 1e-9)
 ROUNDING_GUARD = 1e-14                                      # a hundred times what two float64 evaluations of a shift differ by
 
 

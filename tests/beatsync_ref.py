@@ -13,6 +13,13 @@ NAN = float("nan")
 LINEAR = 0.01
 INTS = ("status", "kin_count", "music_count", "matched", "dropped", "anchors", "rate_min_frame", "rate_max_frame")
 FLOATS = ("shift_max", "rate_min", "rate_max")
+# the bounds the GPU tests hold the kernels to (tests/test_beatsync_gpu.py, tests/test_post_chain_gpu.py):
+# 4 x the largest difference seen over test_beatsync_gpu's SHAPES x share x contacts on an MI355X, as printed by its
+# test_beat_sync_against_the_restatement and kept in profiles/beatsync.txt: the rotations against the restatement's float64 rotation vectors
+# (the one float32 rounding of a rotation vector whose components stay below 0.5: 2^-26 sqrt(3) = 2.6e-8 rad), the joints against a float64 FK
+# of the returned float32 poses
+ROT_MEASURED, FK_MEASURED = 2.53e-8, 7.81e-7
+ROT_BOUND, FK_BOUND = 4 * ROT_MEASURED, 4 * FK_MEASURED
 
 
 def gaussian_table(sigma):

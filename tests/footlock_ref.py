@@ -10,6 +10,9 @@ from tcdiff_amd.fk import SMPL_OFFSETS, SMPL_PARENTS
 
 LEGS = ((1, 4, 7, 10), (2, 5, 8, 11))          # hip, knee, ankle, toe
 SMALL, TINY = 1e-3, 1e-9
+# the bounds the GPU tests hold the kernels to (tests/test_footlock_gpu.py, tests/test_post_chain_gpu.py)
+ROT_BOUND = 1e-6          # the one float32 rounding is 2^-24 pi sqrt(3) = 3.3e-7 rad; a wrong formula errs by 1e-3 or more
+PIN_BOUND = 2e-6          # three joints and the pelvis at 3.3e-7 rad over a lever of at most 0.95 m: below 1e-6 m
 
 
 # ---- vectors and quaternions (w, x, y, z) as tuples of floats -----------------------------------------------------------------------------

@@ -12,6 +12,9 @@ J = 24
 SMALL = 1e-3                              # TCK_SMALL: the series of sin(theta / 2) / theta below it
 MIN_NORM = 1e-6
 ALL = (1 << 24) - 1
+# the bounds the GPU tests hold the kernels to (tests/test_smooth_gpu.py, tests/test_post_chain_gpu.py)
+ROT_BOUND = 1e-6          # the one float32 rounding is 2^-24 pi sqrt(3) = 3.3e-7 rad, as tests/test_footlock_gpu.py
+FK_BOUND = 1e-5
 FLOATS = ("accel_mean", "jitter", "jitter_local", "root_jitter", "accel_max", "jitter_max")
 INTS = ("accel_peak", "jitter_peak", "terms")
 

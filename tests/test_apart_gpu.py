@@ -29,8 +29,7 @@ from tcdiff_amd.group_metrics import group_metrics
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-MEASURED = 0.0            # metres: the largest difference of a float64 output from the restatement over every case here (profiles/apart.txt)
-FLOAT_BOUND = min(100 * MEASURED, 1e-9)
+MEASURED, FLOAT_BOUND = A.MEASURED, A.FLOAT_BOUND          # in tests/apart_ref.py: tests/test_post_chain_gpu.py holds the chain to the same bound
 INTS = ("contact_before", "contact_after", "pushed", "capped")
 FLOATS = ("shift", "max_shift", "max_step", "gap_min_before", "gap_min_after")
 _want = {}

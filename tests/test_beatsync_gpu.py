@@ -25,11 +25,7 @@ from tcdiff_amd.metrics import motion_metrics
 B = importlib.import_module("tcdiff_amd.beat_sync")                # the package's attribute of this name is the function
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-# 4 x the largest difference seen over SHAPES x share x contacts on an MI355X, as printed by test_beat_sync_against_the_restatement and
-# kept in profiles/beatsync.txt: the rotations against the restatement's float64 rotation vectors (the one float32 rounding of a
-# rotation vector whose components stay below 0.5: 2^-26 sqrt(3) = 2.6e-8 rad), the joints against a float64 FK of the returned float32 poses
-ROT_MEASURED, FK_MEASURED = 2.53e-8, 7.81e-7
-ROT_BOUND, FK_BOUND = 4 * ROT_MEASURED, 4 * FK_MEASURED
+ROT_BOUND, FK_BOUND = R.ROT_BOUND, R.FK_BOUND          # in tests/beatsync_ref.py: tests/test_post_chain_gpu.py holds the chain to the same two
 SHAPES = [(1, 1, 2), (1, 1, 4), (2, 3, 65), (1, 2, 257), (1, 3, 300)]
 PER_WARP = ("warp", "speed", "kin", "status", "kin_count", "music_count", "matched", "dropped", "anchors", "shift_max", "rate_min", "rate_max",
             "rate_min_frame", "rate_max_frame")

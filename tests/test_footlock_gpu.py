@@ -22,8 +22,7 @@ from tcdiff_amd.metrics import motion_metrics
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 DN = R.DN
-ROT_BOUND = 1e-6          # the one float32 rounding is 2^-24 pi sqrt(3) = 3.3e-7 rad; a wrong formula errs by 1e-3 or more
-PIN_BOUND = 2e-6          # three joints and the pelvis at 3.3e-7 rad over a lever of at most 0.95 m: below 1e-6 m
+ROT_BOUND, PIN_BOUND = R.ROT_BOUND, R.PIN_BOUND          # with their reasons in tests/footlock_ref.py: tests/test_post_chain_gpu.py holds the chain to the same two
 LEG_JOINTS = [1, 4, 7, 2, 5, 8]
 OTHERS = [j for j in range(24) if j not in LEG_JOINTS]
 

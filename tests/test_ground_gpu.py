@@ -29,8 +29,7 @@ from tcdiff_amd import kernels as K
 P = importlib.import_module("tcdiff_amd.ground")          # the module: the package's attribute `ground` is the function
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-MEASURED = 0.0            # metres: the largest difference of a float64 output from the restatement over every case here (profiles/ground.txt)
-FLOAT_BOUND = min(100 * MEASURED, 1e-9)
+MEASURED, FLOAT_BOUND = R.MEASURED, R.FLOAT_BOUND          # in tests/ground_ref.py: tests/test_post_chain_gpu.py holds the chain to the same bound
 _want = {}
 _worst = {"f64": 0.0, "ulp": 0}
 

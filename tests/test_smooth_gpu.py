@@ -26,8 +26,7 @@ from tcdiff_amd.fk import SMPL_OFFSETS, SMPL_PARENTS
 S = importlib.import_module("tcdiff_amd.smooth")                   # the package's attribute of this name is the function
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-ROT_BOUND = 1e-6          # the one float32 rounding is 2^-24 pi sqrt(3) = 3.3e-7 rad, as tests/test_footlock_gpu.py
-FK_BOUND = 1e-5
+ROT_BOUND, FK_BOUND = R.ROT_BOUND, R.FK_BOUND          # in tests/smooth_ref.py: tests/test_post_chain_gpu.py holds the chain to the same two
 MASK_16_23 = sum(1 << j for j in range(16, 24))
 # name -> (b, dn, T, keywords): all edge rows with no or one interior frame, the tile boundary, two tiles and a tail, the largest LDS
 # footprint, the smallest window, two clips, one to three dancers, another root window, a mask
